@@ -4,7 +4,7 @@
 seq 1024, 8 labels — one process per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|f16|bf16] [--config base|small|large|qwen-1.5b|c2|c3|c4|c5]
-                  [--batch B] [--seq S] [--labels C] [--scaling weak|strong]
+                  [--batch B] [--seq S] [--labels C] [--scaling weak|strong] [--full] [--dump-outputs DIR]
   (--config c2 .. c5 = BASELINE.json's configs as one flag: c4 = large, one global batch of 256 split over the ranks, strong scaling)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -19,10 +19,17 @@ A step = one forward over one batch whose token ids / mask are already resident 
                    GPU) and every step ends with the gather of the [B/G, C] logits to rank 0 (RCCL all-gather); value = B*K / time.
 
 The headline mode is the DEFAULT arithmetic mode of the product (GLICLASS_DTYPE unset = f32: fp32 data, every matrix product as
-split-f16 MFMAs), the mode that meets the 1e-3 probability tolerance; rank 0 checks it live against the CPU oracle and prints
-`parity_ok`.  The opt-in 16-bit throughput mode is measured beside it (`throughput_mode`), flagged with its own error.
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, HIP-event timed on the engine's stream) and `cpu_baseline`
-(the C oracle — a port, not ONNXRuntime — on a bounded sample of the same workload).
+split-f16 MFMAs), the mode that meets the 1e-3 probability tolerance.  A plain run does only what the headline figure needs: it sets
+up, warms up, times the K steps and rank 0 prints ONE JSON line (`value`, `ms_per_step`, ...; `parity_ok` is null: no oracle leg ran).
+
+  --full           everything else, after the timed steps: the HIP-event cross-check and per-step distribution of the same loop,
+                   the boundary-inclusive steps (host_buffer_ms_per_step, serving_loop_ms_per_step), the gather alone (strong mode),
+                   `roofline` (dominant kernel, HIP-event timed on the engine's stream), `cpu_baseline` (the C oracle — a port, not
+                   ONNXRuntime — on a bounded sample of the same workload) with the live parity check against it (`parity_ok`), and
+                   the opt-in 16-bit throughput mode beside the headline (`throughput_mode`, flagged with its own error).
+  --dump-outputs DIR  rank 0 writes what the timed path returned in its LAST timed step: DIR/logits.npy, the [B, C] float32 logits
+                   (strong mode: the gathered global batch).  Weights and inputs are seeded, so two builds run with the same
+                   arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -346,6 +353,21 @@ def profile_mode(hipl, h, step, sync, cfg, B, S, Cn, dtype, seqs_per_s_one_gpu, 
                 per_kernel=per)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32; one larger than the 64 MB budget is cut to a fixed, seeded sample of its
+    rows (the same rows on every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > DUMP_CAP_BYTES:
+            keep = DUMP_CAP_BYTES // (a.nbytes // a.shape[0])
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def prob_err(a, b):
     return float(np.abs(1 / (1 + np.exp(-a.astype(np.float64))) - 1 / (1 + np.exp(-b.astype(np.float64)))).max())
 
@@ -357,16 +379,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dtype", default=os.environ.get("GLICLASS_DTYPE", "f32"), choices=["f32", "f16", "bf16"],
                     help="arithmetic mode of the headline number (default: the product's default, f32 = split-f16 MFMA products)")
-    ap.add_argument("--throughput-dtype", default="f16", choices=["f16", "bf16", "none"], help="opt-in 16-bit mode measured beside the headline (N=1)")
+    ap.add_argument("--throughput-dtype", default="f16", choices=["f16", "bf16", "none"], help="--full: opt-in 16-bit mode measured beside the headline (N=1)")
     ap.add_argument("--config", default="base")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--labels", type=int, default=8)
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"])
     ap.add_argument("--dump-logits", default="", help=argparse.SUPPRESS)      # tests: rank 0 writes the step's [B, C] logits (.npy)
-    ap.add_argument("--cpu-seqs", type=int, default=12, help="sequences timed on the CPU baseline, N=1 only (0 = skip); 12 = about 10 s on a 16-CPU share")
-    ap.add_argument("--cpu-seqs-8", type=int, default=6, help="sequences of the OMP_NUM_THREADS=8 leg of the CPU baseline")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/logits.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run the cross-checks, boundary steps, roofline profile, CPU baseline + parity and "
+                                                         "the 16-bit throughput mode (a plain run times the steps and nothing else)")
+    ap.add_argument("--cpu-seqs", type=int, default=12, help="--full: sequences timed on the CPU baseline, N=1 only (0 = skip); 12 = about 10 s on a 16-CPU share")
+    ap.add_argument("--cpu-seqs-8", type=int, default=6, help="--full: sequences of the OMP_NUM_THREADS=8 leg of the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: no roofline profile")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)        # CPU rehearsal of the multi-rank path (tests): gloo + StubRunner
     args = ap.parse_args()
     # BASELINE.json's configs as one flag each (explicit --batch / --seq / --scaling still win where given on the command line)
@@ -479,49 +504,53 @@ def main():
     rank_ms = {"min": round(-max_over_ranks(-own_ms), 3), "max": round(max_over_ranks(own_ms), 3)}
     omp_threads = int(os.environ.get("OMP_NUM_THREADS", "1"))
     assert omp_threads >= 1, "host threads per rank"
+    # what the timed path returned in its LAST timed step (rank 0; strong mode: the gathered global batch), copied out before anything
+    # else runs on the engine: the --dump-outputs arrays and the logits every --full check below compares against
+    logits = None
+    if rank == 0:
+        logits = (gathered[0] if gathered[0] is not None else runner.logits).detach().cpu().numpy().copy()
 
     out = None
     if args.stub:
         if rank == 0:
-            full = gathered[0] if gathered[0] is not None else runner.logits
             out = {"metric": "stub", "value": round(seqs_per_s, 2), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                    "scaling": args.scaling, "global_batch": global_rows, "rows_rank0": B, "step_calls_rank0": runner.calls,
                    "rank_ms_per_step": rank_ms, "omp_threads_per_rank": omp_threads,
-                   "gathered_rows": [int(v) for v in (full[:, 0] / 16).tolist()] if args.scaling == "strong" else None}
+                   "gathered_rows": [int(v) for v in (logits[:, 0] / 16).tolist()] if args.scaling == "strong" else None}
     else:
         h = runner.h
-        # HIP-event cross-check of the same loop on this rank's stream
-        hipl.glc_timer_start(h)
-        for _ in range(args.steps):
-            runner.step()
-        ev_ms = float(hipl.glc_timer_stop_ms(h)) / args.steps
-        # per-step distribution (SURVEY.md §8d protocol: median + p10 / p90): every step timed on its own with HIP events on the engine's stream
+        ev_ms = gather_ms = None
         lap = []
-        for _ in range(max(5, min(args.steps, 20))):
+        if args.full:
+            # HIP-event cross-check of the same loop on this rank's stream
             hipl.glc_timer_start(h)
-            runner.step()
-            lap.append(float(hipl.glc_timer_stop_ms(h)))
-        lap.sort()
+            for _ in range(args.steps):
+                runner.step()
+            ev_ms = float(hipl.glc_timer_stop_ms(h)) / args.steps
+            # per-step distribution (SURVEY.md §8d protocol: median + p10 / p90): every step timed on its own with HIP events on the engine's stream
+            for _ in range(max(5, min(args.steps, 20))):
+                hipl.glc_timer_start(h)
+                runner.step()
+                lap.append(float(hipl.glc_timer_stop_ms(h)))
+            lap.sort()
+            if args.scaling == "strong" and dist is not None:        # the collective alone, HIP-event free (host clock, synchronous)
+                runner.sync()
+                t0 = time.perf_counter()
+                for _ in range(20):
+                    gather_logits(dist, runner, world, rank, global_rows, Cn)
+                torch.cuda.synchronize()
+                gather_ms = (time.perf_counter() - t0) / 20 * 1e3
         pct = lambda q: lap[min(len(lap) - 1, int(round(q * (len(lap) - 1))))]
-        gather_ms = None
-        if args.scaling == "strong" and dist is not None:        # the collective alone, HIP-event free (host clock, synchronous)
-            runner.sync()
-            t0 = time.perf_counter()
-            for _ in range(20):
-                gather_logits(dist, runner, world, rank, global_rows, Cn)
-            torch.cuda.synchronize()
-            gather_ms = (time.perf_counter() - t0) / 20 * 1e3
         if rank == 0:
-            logits = (gathered[0] if gathered[0] is not None else runner.logits).cpu().numpy()
             key = f"{args.config}:{args.batch}:{S}"
             roof = None
             mx_on = bool(hipl.glc_debug_last_forward_mx(h)) if args.dtype == "f32" else False
             mx_attn_on = bool(hipl.glc_debug_last_forward_mx_attention(h)) if mx_on else False
-            if not args.no_profile:
+            if args.full and not args.no_profile:
                 roof = profile_mode(hipl, h, runner.step, runner.sync, cfg, B, S, Cn, args.dtype, B / (ev_ms * 1e-3), key, mx_on, mx_attn_on)
             # boundary-inclusive step (SURVEY.md §8d protocol): host int64 ids/mask in, H2D, forward, D2H of the logits out
             host_ms = None
-            if world == 1:
+            if args.full and world == 1:
                 hl = np.zeros((B, Cn), np.float32)
                 c_out = C.c_int(0)
                 hipl.glc_engine_forward(h, ids.ctypes.data, mask.ctypes.data, B, S, hl.ctypes.data, Cn, C.byref(c_out))
@@ -532,7 +561,7 @@ def main():
             # ... and the same boundary as a serving loop would drive it: the NEXT batch's int64 ids / mask go host -> device on a copy
             # stream (pinned buffers, two device slots) while this batch's forward runs; every step ends with the logits on the host
             serve_ms = None
-            if world == 1:
+            if args.full and world == 1:
                 try:
                     dev = f"cuda:{local_rank}"
                     pin_i, pin_m = torch.from_numpy(ids).pin_memory(), torch.from_numpy(mask).pin_memory()
@@ -567,7 +596,7 @@ def main():
                     print(f"bench: serving-loop leg skipped ({e})", file=sys.stderr)
             cpu = None
             ref_logits = rids = rmask = None
-            if args.cpu_seqs > 0 and world == 1:
+            if args.full and args.cpu_seqs > 0 and world == 1:
                 print(f"bench: CPU baseline leg ({min(args.cpu_seqs, B)} + {args.cpu_seqs_8} sequences on the oracle) ...", file=sys.stderr, flush=True)
                 cpu, ref_logits, rids, rmask = cpu_baseline(cfg, W.tensors, S, Cn, min(args.cpu_seqs, B), args.cpu_seqs_8)
                 # parity check of the timed configuration itself: same seed => the oracle's rows are the first rows of the timed batch
@@ -592,15 +621,14 @@ def main():
                            "parallelism": (f"batch-shard x{world}: one process per GPU, every rank a full batch, no data-path collective" if args.scaling == "weak" else
                                            f"batch-shard x{world}: one global batch split contiguously ({B} rows on rank 0), logits all-gathered to rank 0 every step (RCCL)")},
                 "rank_ms_per_step": rank_ms, "omp_threads_per_rank": omp_threads,
-                "hip_event_ms_per_step": round(ev_ms, 3),
-                "step_ms_median": round(pct(0.5), 3), "step_ms_p10": round(pct(0.1), 3), "step_ms_p90": round(pct(0.9), 3), "step_ms_samples": len(lap),
                 "finite": bool(np.isfinite(logits).all()),
             }
+            if ev_ms is not None:
+                out["hip_event_ms_per_step"] = round(ev_ms, 3)
+                out.update(step_ms_median=round(pct(0.5), 3), step_ms_p10=round(pct(0.1), 3), step_ms_p90=round(pct(0.9), 3), step_ms_samples=len(lap))
             if world > 1 and scaling_defaulted:
                 out["config"]["parallelism"] += ("; BASELINE.json's c4 (one global batch of 256 split 32 per GPU, logits gathered) is "
                                                  "`bench.py --config c4 --gpus N` (= --config large --batch 256 --scaling strong)")
-            if args.dump_logits:
-                np.save(args.dump_logits, logits)
             if host_ms is not None:
                 out["host_buffer_ms_per_step"] = round(host_ms, 3)     # H2D of ids/mask + forward + D2H of logits (glc_engine_forward)
             if serve_ms is not None:
@@ -614,7 +642,7 @@ def main():
                 out["parity_ok"] = bool(cpu["gpu_vs_cpu_max_prob_err"] <= BAR)
                 out["parity_bar"] = BAR
             else:
-                out["parity_ok"] = None           # the oracle leg was skipped (--cpu-seqs 0 or N > 1): this line carries no parity evidence
+                out["parity_ok"] = None           # no oracle leg (a plain run, --cpu-seqs 0 or N > 1): this line carries no parity evidence
             tdt = args.throughput_dtype
             if cpu and world == 1 and tdt != "none" and tdt != args.dtype:
                 # The opt-in 16-bit throughput mode on the same workload: reported beside the headline number, never instead of
@@ -647,6 +675,10 @@ def main():
         barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_logits:
+            np.save(args.dump_logits, logits)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"logits": logits})
         print(json.dumps(out), flush=True)
 
 

@@ -7,7 +7,7 @@ for mode in "native native" "split native" "split split"; do
   set -- $mode; gm=$1; am=$2
   for cfg in "base 64 1024" "small 8 512"; do
     set -- $cfg
-    GLICLASS_F32_GEMM=$gm GLICLASS_F32_ATTN=$am python bench.py --dtype f32 --config $1 --batch $2 --seq $3 --steps 5 --warmup 2 --cpu-seqs 1 2>/dev/null | python -c "
+    GLICLASS_F32_GEMM=$gm GLICLASS_F32_ATTN=$am python bench.py --full --dtype f32 --config $1 --batch $2 --seq $3 --steps 5 --warmup 2 --cpu-seqs 1 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); pk=d['roofline']['per_kernel']
 print('gemm=$gm attn=$am', '$1', d['value'], d['ms_per_step'], 'err', d['cpu_baseline'].get('gpu_vs_cpu_max_prob_err'), {k: pk[k]['avg_ms'] for k in ('attention','gemm_qkv','gemm_ffn1_gelu','gemm_ffn2','gemm_attn_out','last_layer_pruned') if k in pk})"
   done

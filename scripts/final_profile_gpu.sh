@@ -14,7 +14,7 @@ OUT=$REPO/gpurun_out/final_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp GLICLASS_BENCH_COMMIT=$COMMIT
 echo "$COMMIT" > "$OUT/commit.txt"
-python3 bench.py > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"; echo "bench rc=$?"
+python3 bench.py --full > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"; echo "bench rc=$?"
 cd /tmp
 BENCH="$REPO/bench.py --steps 3 --warmup 1 --cpu-seqs 0 --no-profile --throughput-dtype none"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace -- python3 $BENCH > "$OUT/trace.log" 2>&1; echo "trace rc=$?"
@@ -65,14 +65,14 @@ print("traffic.json:", {k: (v.get("source"), v.get("commit"), sorted(v.get("kern
 PY
 rm -rf "$OUT/f16/pmc_fetch" "$OUT/f16/pmc_write"
 # (round 5, review item 7) config c5 (decoder backbone, B = 16, S = 2048) of the same build: bench line + rocprofv3 kernel stats
-python3 bench.py --config c5 --cpu-seqs 0 --throughput-dtype none > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"; echo "c5 bench rc=$?"
+python3 bench.py --full --config c5 --cpu-seqs 0 --throughput-dtype none > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err"; echo "c5 bench rc=$?"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_c5" -o trace -- python3 $REPO/bench.py --config c5 --steps 2 --warmup 1 --cpu-seqs 0 --no-profile --throughput-dtype none > "$OUT/trace_c5.log" 2>&1; echo "c5 trace rc=$?"
 cd "$REPO"
 find "$OUT/trace_c5" -name "*kernel_stats.csv" -exec cp {} "$OUT/c5_kernel_stats.csv" \;
 rm -rf "$OUT/trace_c5"
 # (round 6, review item 6) BASELINE.json's c4 as ONE GPU sees it: gliclass-large, 32 rows of 1024 — bench line + kernel stats
-python3 bench.py --config large --batch 32 --cpu-seqs 0 --throughput-dtype none > "$OUT/bench_c4_shard.json" 2> "$OUT/bench_c4_shard.err"; echo "c4 shard bench rc=$?"
+python3 bench.py --full --config large --batch 32 --cpu-seqs 0 --throughput-dtype none > "$OUT/bench_c4_shard.json" 2> "$OUT/bench_c4_shard.err"; echo "c4 shard bench rc=$?"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_c4" -o trace -- python3 $REPO/bench.py --config large --batch 32 --steps 2 --warmup 1 --cpu-seqs 0 --no-profile --throughput-dtype none > "$OUT/trace_c4.log" 2>&1; echo "c4 trace rc=$?"
 cd "$REPO"

@@ -3,7 +3,7 @@ set -u
 REPO=$(pwd); OUT=$REPO/gpurun_out/l2; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 for ORD in 0 1 2; do
   export GLC_GEMM_ORDER=$ORD
-  python3 $REPO/bench.py --steps 3 --warmup 1 --cpu-seqs 0 > $OUT/bench_o$ORD.json 2>/dev/null
+  python3 $REPO/bench.py --full --steps 3 --warmup 1 --cpu-seqs 0 > $OUT/bench_o$ORD.json 2>/dev/null
   python3 -c "
 import json; d=json.load(open('$OUT/bench_o$ORD.json')); pk=d['roofline']['per_kernel']; print('order $ORD', d['ms_per_step'], {k: pk[k]['avg_ms'] for k in pk if 'gemm' in k})"
   rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --kernel-trace --output-format csv -d $OUT/o$ORD -o pmc -- python3 $REPO/bench.py --steps 1 --warmup 1 --cpu-seqs 0 --no-profile > $OUT/o$ORD.log 2>&1

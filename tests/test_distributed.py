@@ -108,6 +108,18 @@ def test_bench_spawns_its_own_ranks_strong_scaling():
     assert out["value"] > 0
 
 
+def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the timed path returned in its last step — the gathered [B, C] logits in strong mode."""
+    import numpy as np
+    out = _run_bench_stub("--gpus", "2", "--scaling", "strong", "--batch", "7", "--labels", "3", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "out"))
+    assert out["steps"] == 3 and out["step_calls_rank0"] == 4
+    assert sorted(os.listdir(tmp_path / "out")) == ["logits.npy"]
+    got = np.load(tmp_path / "out" / "logits.npy")
+    assert got.dtype == np.float32
+    assert np.array_equal(got, np.arange(7, dtype=np.float32)[:, None] * 16 + np.arange(3, dtype=np.float32)[None, :])
+
+
 def test_bench_spawns_its_own_ranks_weak_scaling():
     out = _run_bench_stub("--gpus", "2", "--scaling", "weak", "--batch", "6", "--labels", "2", "--steps", "4", "--warmup", "1")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["global_batch"] == 12 and out["rows_rank0"] == 6
