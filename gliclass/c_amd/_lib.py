@@ -19,7 +19,8 @@ class ModelConfig(C.Structure):
                                          "max_rel_pos", "pad_id", "cls_id", "sep_id", "class_token_index",
                                          "text_token_index", "pooling", "scorer", "embed_class_token",
                                          "normalize_features", "backbone", "kv_heads", "causal")] + \
-               [("ln_eps", C.c_float), ("logit_scale", C.c_float), ("rope_theta", C.c_float)]
+               [("ln_eps", C.c_float), ("logit_scale", C.c_float), ("rope_theta", C.c_float),
+                ("local_window", C.c_int32), ("global_every", C.c_int32), ("rope_theta_local", C.c_float)]
 
 
 class Weights(C.Structure):

@@ -15,7 +15,7 @@ SCORER_WEIGHTED_DOT = 1
 SCORER_MLP = 2
 SCORER_MLP_HIDDEN = 256
 SCORER_NAMES = {"simple": SCORER_DOT, "weighted-dot": SCORER_WEIGHTED_DOT, "mlp": SCORER_MLP}
-BACKBONE_DEBERTA, BACKBONE_DECODER = 0, 1
+BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT = 0, 1, 2
 
 
 @dataclass(frozen=True)
@@ -46,6 +46,12 @@ class GLiClassConfig:
     kv_heads: int = 0               # 0 => heads (no grouping)
     causal: int = 1                 # BASELINE.json says causal; upstream may wrap decoders bidirectionally (unpinned) -> flag
     rope_theta: float = 1.0e6
+    # ModernBERT backbone (transformers models/modernbert): rope_theta is the global layers' base, rope_theta_local the local
+    # layers'; a local layer attends to keys with |q - k| <= local_window (= local_attention // 2; 0 = every layer global);
+    # layer l is global when l % global_every == 0; ln_eps is norm_eps, `inter` the GeGLU width
+    local_window: int = 0
+    global_every: int = 1
+    rope_theta_local: float = 1.0e4
 
     def __post_init__(self):
         assert self.hidden == self.heads * self.head_dim
@@ -63,12 +69,20 @@ class GLiClassConfig:
 
     def flops_per_seq(self, S: int, C: int) -> float:
         """F_seq = L*S*(8H^2 + 4HI + 4SH + 4PH) + 8H^2(1+C); decoder:
-        L*S*(4H*nq*d + 4H*nkv*d + 6HI + 4S*nq*d*kappa) + head, kappa = 1/2 when causal."""
+        L*S*(4H*nq*d + 4H*nkv*d + 6HI + 4S*nq*d*kappa) + head, kappa = 1/2 when causal; ModernBERT:
+        L*S*(8H^2 + 6HI) + sum_l 4*S*H*keys_l + head, keys_l = S on global layers and min(S, 2W+1) on local ones."""
         H, I, L, P = self.hidden, self.inter, self.layers, 2 * self.att_span
+        if self.backbone == BACKBONE_MODERNBERT:
+            keys = sum(S if self.is_global_layer(l) else min(S, 2 * self.local_window + 1) for l in range(L))
+            return L * S * (8 * H * H + 6 * H * I) + 4 * S * H * keys + 8 * H * H * (1 + C)
         if self.backbone == BACKBONE_DECODER:
             nqd, nkvd, kappa = self.heads * self.head_dim, self.kv_heads * self.head_dim, (0.5 if self.causal else 1.0)
             return L * S * (4 * H * nqd + 4 * H * nkvd + 6 * H * I + 4 * S * nqd * kappa) + 8 * H * H * (1 + C)
         return L * S * (8 * H * H + 4 * H * I + 4 * S * H + 4 * P * H) + 8 * H * H * (1 + C)
+
+    def is_global_layer(self, l: int) -> bool:
+        """ModernBERT: full attention (and the global RoPE base) on layer l."""
+        return self.local_window <= 0 or l % max(self.global_every, 1) == 0
 
     def asdict(self):
         return asdict(self)
@@ -90,4 +104,16 @@ CONFIGS = {
                                ln_eps=1e-6, backbone=BACKBONE_DECODER, pooling=POOL_LAST),
     "qwen-1.5b": GLiClassConfig("qwen-1.5b", vocab=151648, hidden=1536, layers=28, heads=12, inter=8960, head_dim=128,
                                 kv_heads=2, ln_eps=1e-6, backbone=BACKBONE_DECODER, pooling=POOL_LAST),
+    # ModernBERT backbones: mb-tiny / mb-mini are the parity-fixture configs (mb-tiny: H % 256 != 0, the paths without group split;
+    # mb-mini: group-split eligible), modernbert-base / -large the published shapes (vocab 50 368 + <<LABEL>>, <<SEP>>)
+    "mb-tiny": GLiClassConfig("mb-tiny", vocab=515, hidden=128, layers=4, heads=2, inter=192, ln_eps=1e-5, backbone=BACKBONE_MODERNBERT,
+                              causal=0, rope_theta=160000.0, local_window=8, global_every=3, rope_theta_local=10000.0),
+    "mb-mini": GLiClassConfig("mb-mini", vocab=1027, hidden=256, layers=4, heads=4, inter=384, ln_eps=1e-5, backbone=BACKBONE_MODERNBERT,
+                              causal=0, rope_theta=160000.0, local_window=64, global_every=3, rope_theta_local=10000.0, pooling=POOL_AVG),
+    "modernbert-base": GLiClassConfig("modernbert-base", vocab=50370, hidden=768, layers=22, heads=12, inter=1152, ln_eps=1e-5,
+                                      backbone=BACKBONE_MODERNBERT, causal=0, rope_theta=160000.0, local_window=64, global_every=3,
+                                      rope_theta_local=10000.0),
+    "modernbert-large": GLiClassConfig("modernbert-large", vocab=50370, hidden=1024, layers=28, heads=16, inter=2624, ln_eps=1e-5,
+                                       backbone=BACKBONE_MODERNBERT, causal=0, rope_theta=160000.0, local_window=64, global_every=3,
+                                       rope_theta_local=10000.0),
 }

@@ -6,7 +6,9 @@
 //   rope_qk       Q2:86-100, 105-109, 133-134  rotate-half RoPE applied in place to the Q and K columns of the fused
 //                 QKV projection; the softmax scale log2(e)/sqrt(d) (Q2:186, :163) is folded into Q here
 //   swiglu        Q2:47       silu(gate) * up on the fused [gate | up] projection
-//   attn_gqa      Q2:160-170  grouped-query attention with causal and key-padding mask (create_causal_mask), exp2 softmax
+//   attn_gqa      Q2:160-170  grouped-query attention with causal and key-padding mask (create_causal_mask), exp2 softmax; with a
+//                 window W (ModernBERT's local layers, modeling_modernbert.py) keys with |q - k| > W are masked and never visited
+//   geglu         ModernBERT MLP: gelu(input) * gate on the fused [input | gate] projection (the SwiGLU kernels with the erf GELU)
 // Row kernels are HBM streams: one wave per row, 16-byte vectors.
 #include "glc_common.h"
 #include "glc_kernels.h"
@@ -90,6 +92,8 @@ __global__ __launch_bounds__(256) void rmsnorm_gs_kernel(const float* __restrict
     }
 }
 // F[m, i] = silu(GU[m, i]) * GU[m, I + i]: plain fp32 [gate | up] rows in, group-split rows out
+// (GELU: gelu(GU[m, i]) * GU[m, I + i], ModernBERT's GeGLU on [input | gate], erf GELU at fp32 resolution as the EPI_GELU epilogue)
+template <bool GELU>
 __global__ __launch_bounds__(256) void swiglu_gs_kernel(const float* __restrict__ GU, f16_t* __restrict__ F, size_t M, int I) {
     const size_t nch = (size_t)I / 8, total = M * nch;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -98,10 +102,18 @@ __global__ __launch_bounds__(256) void swiglu_gs_kernel(const float* __restrict_
         const f32x4 g0 = *reinterpret_cast<const f32x4*>(g), g1 = *reinterpret_cast<const f32x4*>(g + 4);
         const f32x4 u0 = *reinterpret_cast<const f32x4*>(g + I), u1 = *reinterpret_cast<const f32x4*>(g + I + 4);
         float o[8];
+        if constexpr (GELU) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            o[e] = g0[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-g0[e])) * u0[e];
-            o[4 + e] = g1[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-g1[e])) * u1[e];
+            for (int e = 0; e < 4; e += 2) {
+                const f32x2 a = glc_gelu2_f32((f32x2){g0[e], g0[e + 1]}), b = glc_gelu2_f32((f32x2){g1[e], g1[e + 1]});
+                o[e] = a[0] * u0[e]; o[e + 1] = a[1] * u0[e + 1]; o[4 + e] = b[0] * u1[e]; o[5 + e] = b[1] * u1[e + 1];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                o[e] = g0[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-g0[e])) * u0[e];
+                o[4 + e] = g1[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-g1[e])) * u1[e];
+            }
         }
         gs_store8(F + m * 2 * I, (int)(ch * 8), o);
     }
@@ -127,10 +139,10 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(T* __restrict__ QKV, const
     }
 }
 
-// F[m, i] = silu(GU[m, i]) * GU[m, I + i]
+// F[m, i] = silu(GU[m, i]) * GU[m, I + i]   (GELU: gelu(GU[m, i]) * GU[m, I + i], ModernBERT's GeGLU, erf GELU in fp32)
 // inter = 1: the [gate | up] columns interleave 16 gate / 16 up features (the fused weight layout of the SwiGLU GEMM epilogue,
 // engine.hip): feature i's gate is column 32 (i / 16) + i % 16, its up column 16 further on
-template <typename T>
+template <typename T, bool GELU = false>
 __global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ GU, T* __restrict__ F, size_t M, int I, int inter) {
     typedef typename Vec16<T>::type vecT;
     constexpr int VEC = Vec16<T>::N;
@@ -142,10 +154,18 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ GU, T
         const vecT g = *reinterpret_cast<const vecT*>(GU + m * 2 * I + gcol);
         const vecT u = *reinterpret_cast<const vecT*>(GU + m * 2 * I + ucol);
         vecT o;
+        if constexpr (GELU) {
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float gv = (float)g[e];
-            o[e] = (T)(gv * __builtin_amdgcn_rcpf(1.0f + __expf(-gv)) * (float)u[e]);
+            for (int e = 0; e < VEC; e += 2) {
+                const f32x2 a = glc_gelu2_f32((f32x2){(float)g[e], (float)g[e + 1]});
+                o[e] = (T)(a[0] * (float)u[e]); o[e + 1] = (T)(a[1] * (float)u[e + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float gv = (float)g[e];
+                o[e] = (T)(gv * __builtin_amdgcn_rcpf(1.0f + __expf(-gv)) * (float)u[e]);
+            }
         }
         *reinterpret_cast<vecT*>(F + m * I + ch * VEC) = o;
     }
@@ -153,10 +173,11 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ GU, T
 
 // Straightforward grouped-query attention (any T, no MFMA): one block per (query row, head).  Q already carries
 // log2(e)/sqrt(d); scores are in log2 units.  Keys j > q are excluded when causal; padded keys carry the -1e30 bias.
+// window > 0: only keys q - window .. q + window are visited (ModernBERT's local layers).
 template <typename T>
 __global__ __launch_bounds__(256) void attn_gqa_simple_kernel(const T* __restrict__ QKV, const float* __restrict__ kbias,
                                                               const int* __restrict__ klen, T* __restrict__ CTX, int Sp, int nq, int nkv,
-                                                              int d, int causal) {
+                                                              int d, int causal, int window) {
     typedef typename Vec16<T>::type vecT;
     constexpr int VEC = Vec16<T>::N;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -175,8 +196,14 @@ __global__ __launch_bounds__(256) void attn_gqa_simple_kernel(const T* __restric
     if (causal && q + 1 < kend) kend = q + 1;
     if (kend < 1) kend = 1;
     if (kend > Sp) kend = Sp;
+    int kbeg = 0;
+    if (window > 0) {
+        if (q + window + 1 < kend) kend = q + window + 1;
+        kbeg = q - window > 0 ? q - window : 0;
+        if (kbeg >= kend) kbeg = kend - 1;          // (a padded query row beyond klen + window: any one key keeps the row finite)
+    }
     float mx = -3.0e38f;
-    for (int k = t; k < kend; k += 256) {
+    for (int k = kbeg + t; k < kend; k += 256) {
         const T* kr = Kb + (size_t)k * ld;
         float s = 0.f;
         for (int e0 = 0; e0 < d; e0 += VEC) {
@@ -194,7 +221,7 @@ __global__ __launch_bounds__(256) void attn_gqa_simple_kernel(const T* __restric
     mx = red[0];
     __syncthreads();
     float sum = 0.f;
-    for (int k = t; k < kend; k += 256) { const float p = __builtin_amdgcn_exp2f(sc[k] - mx); sc[k] = p; sum += p; }
+    for (int k = kbeg + t; k < kend; k += 256) { const float p = __builtin_amdgcn_exp2f(sc[k] - mx); sc[k] = p; sum += p; }
     red[t] = sum;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (t < o) red[t] += red[t + o]; __syncthreads(); }
@@ -203,7 +230,7 @@ __global__ __launch_bounds__(256) void attn_gqa_simple_kernel(const T* __restric
     // O[dd] = sum_k p_k V[k][dd]: 256 threads = (256/d) key phases x d columns (d = 64 or 128)
     const int dd = t % d, part = t / d, nparts = 256 / d;
     float acc = 0.f;
-    for (int k = part; k < kend; k += nparts) acc += sc[k] * (float)Vb[(size_t)k * ld + dd];
+    for (int k = kbeg + part; k < kend; k += nparts) acc += sc[k] * (float)Vb[(size_t)k * ld + dd];
     red[t] = acc;
     __syncthreads();
     if (t < d) {
@@ -245,13 +272,15 @@ const char* glc_launch_rmsnorm_gs(hipStream_t st, const float* X, void* Y, const
     hipLaunchKernelGGL(rmsnorm_gs_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, (f16_t*)Y, w, eps, M, H);
     return nullptr;
 }
-const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) {
-    if (!GU || !F || M == 0 || I <= 0 || I % 32) return "swiglu_gs: bad args";
+template <bool GELU> static const char* launch_glu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) {
+    if (!GU || !F || M == 0 || I <= 0 || I % 32) return GELU ? "geglu_gs: bad args" : "swiglu_gs: bad args";
     const size_t total = M * ((size_t)I / 8);
     const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(swiglu_gs_kernel, dim3(grid), dim3(256), 0, st, GU, (f16_t*)F, M, I);
+    hipLaunchKernelGGL(swiglu_gs_kernel<GELU>, dim3(grid), dim3(256), 0, st, GU, (f16_t*)F, M, I);
     return nullptr;
 }
+const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<false>(st, GU, F, M, I); }
+const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<true>(st, GU, F, M, I); }
 
 const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale) {
     if (M <= 0 || Sp <= 0 || !QKV || !cs || nq <= 0 || nkv <= 0 || d <= 0 || d % 2) return "rope: bad args";
@@ -259,28 +288,30 @@ const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float
     return nullptr;
 }
 
-const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) {
-    if (M == 0 || I <= 0 || I % 8 || !GU || !F) return "swiglu: bad args";
+template <bool GELU> static const char* launch_glu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) {
+    if (M == 0 || I <= 0 || I % 8 || (inter && I % 16) || !GU || !F) return GELU ? "geglu: bad args" : "swiglu: bad args";
     DISPATCH_T(dtype, {
         const size_t total = M * ((size_t)I / Vec16<T>::N);
         size_t blocks = (total + 255) / 256;
         if (blocks > 256 * 64) blocks = 256 * 64;
-        hipLaunchKernelGGL(swiglu_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)GU, (T*)F, M, I, inter);
+        hipLaunchKernelGGL((swiglu_kernel<T, GELU>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)GU, (T*)F, M, I, inter);
     });
     return nullptr;
 }
+const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<false>(st, dtype, GU, F, M, I, inter); }
+const char* glc_launch_geglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<true>(st, dtype, GU, F, M, I, inter); }
 
 // impl: 1 = straightforward kernel (any T)
 const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const void* QKV, const float* kbias, const int* klen, void* CTX,
-                                     int B, int Sp, int nq, int nkv, int d, int causal) {
-    if (!QKV || !kbias || !klen || !CTX || B <= 0 || Sp <= 0 || nq <= 0 || nkv <= 0 || nq % nkv) return "attention_gqa: bad args";
+                                     int B, int Sp, int nq, int nkv, int d, int causal, int window) {
+    if (!QKV || !kbias || !klen || !CTX || B <= 0 || Sp <= 0 || nq <= 0 || nkv <= 0 || nq % nkv || window < 0) return "attention_gqa: bad args";
     if (d != 64 && d != 128) return "attention_gqa: head_dim must be 64 or 128";
     if (impl != 1) return "attention_gqa: unknown implementation";
     const size_t shm = (size_t)(d + 256 + Sp) * sizeof(float);
     if (shm > 64 * 1024) return "attention_gqa(simple): sequence too long for the straightforward kernel";
     DISPATCH_T(dtype, {
         hipLaunchKernelGGL(attn_gqa_simple_kernel<T>, dim3(Sp, nq, B), dim3(256), shm, st, (const T*)QKV, kbias, klen, (T*)CTX, Sp, nq, nkv, d,
-                           causal);
+                           causal, window);
     });
     return nullptr;
 }
@@ -299,7 +330,10 @@ const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const 
 // LDS and no workgroup barrier:  S^T = K Q^T (D/16 MFMA 32x32x16), online softmax in log2 units with the deferred rescale of
 // attention.hip, O^T += V^T P^T (D/16 MFMA, P^T taken straight from the S^T accumulators thanks to the pi row order of K).
 // Causal: key tiles above the diagonal are never visited, the diagonal tile masks key > query per element; padded keys
-// carry the additive -1e30 bias on tiles at / after the first masked key.  Grouped queries: head h reads K/V of group
+// carry the additive -1e30 bias on tiles at / after the first masked key.  WIN (ModernBERT's local layers, bidirectional):
+// a wave visits only the key tiles floor((q0 - W) / 32) .. floor((q0 + 31 + W) / 32) that hold keys within |q - k| <= W of
+// its 32 queries; the per-element |q - k| > W mask runs on the edge tiles only (a wave-uniform branch), interior tiles take
+// no compare.  Grouped queries: head h reads K/V of group
 // h / (nq/nkv); the grid keeps all query heads of one (batch, group) on one XCD so they share that group's K/V in L2.
 // =====================================================================================================================
 #include "glc_layout.h"
@@ -383,11 +417,12 @@ template <bool SPLIT, typename T> struct GqaFrag { typedef typename Frag<T>::typ
 template <typename T> struct GqaFrag<true, T> { typedef f16x8s type; };
 // SPLIT (T = float): operands are split-f16 units, every product is three f16 MFMAs (glc_common.h), the probabilities are split on
 // the fly; one wave per SIMD (the doubled fragment sets need > 256 registers at D = 128).
-template <typename T, int D, bool SPLIT = false>
+// WIN: sliding window of half-width `win` (keys with |q - k| > win masked), see above; WIN = false ignores `win`.
+template <typename T, int D, bool SPLIT = false, bool WIN = false>
 __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const T* __restrict__ Qf, const T* __restrict__ Kf, const T* __restrict__ Vt,
                                                                const float* __restrict__ kbias, const int* __restrict__ klen,
                                                                const int* __restrict__ kfirst_, T* __restrict__ CTX, int B, int Sp, int nq,
-                                                               int nkv, int causal, int ctx_gs, unsigned* gx_sat, int act_sc) {
+                                                               int nkv, int causal, int ctx_gs, unsigned* gx_sat, int act_sc, int win = 0) {
     static_assert(!SPLIT || sizeof(T) == 4, "split units live in the fp32 layouts");
     typedef typename GqaFrag<SPLIT, T>::type frag_t;
     constexpr int NS = D / 16, ND = D / 32;
@@ -401,9 +436,10 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
     if (bg >= B * nkv) return;
     const int b = bg / nkv, g = bg - b * nkv;
     const int hq = g * grp + rem / nqb;
-    // longest tiles first within a head (causal work grows with the tile index)
-    const int qt = nt - 1 - ((rem % nqb) * 4 + wave);
-    if (qt < 0) return;
+    // longest tiles first within a head (causal work grows with the tile index); windowed work is uniform over the tiles (but the
+    // edge tiles of a sequence): ascending order, so that the waves of a block and consecutive blocks share most of their key tiles in L2
+    const int qt = WIN ? (rem % nqb) * 4 + wave : nt - 1 - ((rem % nqb) * 4 + wave);
+    if (qt < 0 || (WIN && qt >= nt)) return;
     const int q0 = qt * 32;
 
     const T* __restrict__ Qp = Qf + (((size_t)(b * nq + hq) * nt + qt) * NS) * 512 + lane * 8;
@@ -422,6 +458,13 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
     int nkt = (klen[b] + 31) >> 5;
     nkt = nkt < 1 ? 1 : (nkt > nt ? nt : nkt);
     if (causal && nkt > qt + 1) nkt = qt + 1;
+    int kt0 = 0;                             // first key tile visited
+    if constexpr (WIN) {
+        kt0 = q0 - win > 0 ? (q0 - win) >> 5 : 0;
+        const int klast = (q0 + 31 + win) >> 5;
+        if (nkt > klast + 1) nkt = klast + 1;
+        if (kt0 > nkt - 1) kt0 = nkt - 1;    // (q0 < klen here, so kt0 <= qt < nkt already; kept as a guard)
+    }
     const int kfirst = kfirst_[b];
     const int foff = 8 * h;
 
@@ -437,8 +480,8 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
 
     frag_t kf[NS];                   // ONE K set: the next tile is loaded into it right after its last MFMA of this tile has issued
 #pragma unroll
-    for (int s = 0; s < NS; ++s) kf[s] = *reinterpret_cast<const frag_t*>(Kp + s * 512);
-    for (int kt = 0; kt < nkt; ++kt) {
+    for (int s = 0; s < NS; ++s) kf[s] = *reinterpret_cast<const frag_t*>(Kp + (size_t)kt0 * NS * 512 + s * 512);
+    for (int kt = kt0; kt < nkt; ++kt) {
         const int ktn = kt + 1 < nkt ? kt + 1 : kt;
         frag_t vt[ND][2];
 #pragma unroll
@@ -470,6 +513,15 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
             for (int i = 0; i < 16; ++i) {
                 const int ko = 16 * (i >> 3) + foff + (i & 7);
                 if (ko > c) sv[i] = GLC_NEG_BIG;
+            }
+        }
+        if constexpr (WIN) {
+            if (q0 + 31 - k0 > win || k0 + 31 - q0 > win) {                // wave-uniform: an edge tile holds pairs beyond the window
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int dq = (q0 + c) - (k0 + 16 * (i >> 3) + foff + (i & 7));
+                    if (dq > win || -dq > win) sv[i] = GLC_NEG_BIG;
+                }
             }
         }
         float mx = fmaxf(fmaxf(sv[0], sv[1]), sv[2]);
@@ -556,9 +608,14 @@ template <typename T, bool SPLIT = false> const char* launch_layout_t(hipStream_
     return nullptr;
 }
 template <typename T, bool SPLIT = false> const char* launch_gqa_t(hipStream_t st, const void* Qf, const void* Kf, const void* Vt, const float* kbias, const int* klen,
-                                               const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0) {
+                                               const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0, int window = 0) {
     const int nt = Sp / 32, nqb = (nt + 3) / 4, per = (nq / nkv) * nqb, bg8 = (B * nkv + 7) / 8 * 8;
     const dim3 grid(per * bg8), block(256);
+    if (window > 0) {           // sliding window (ModernBERT, head_dim 64, bidirectional)
+        if (d != 64 || causal) return "attention_gqa_mfma: the windowed kernel takes head_dim 64 and no causal mask";
+        hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, (unsigned*)nullptr, 0, window);
+        return nullptr;
+    }
     if (d == 128) hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 128, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc());
     else hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc());
     return nullptr;
@@ -578,12 +635,13 @@ const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, co
 
 // MFMA grouped-query attention on the fragment-major operands written by glc_launch_qkv_layout.  CTX [B*Sp, nq*d] row-major.
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
-                                          const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs) {
+                                          const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs,
+                                          int window) {
     if (!Qf || !Kf || !Vt || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv ||
-        (d != 64 && d != 128))
+        (d != 64 && d != 128) || window < 0 || (window > 0 && ctx_gs == 2))
         return "attention_gqa_mfma: bad args";
-    if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal);
-    if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal);
-    if (dtype == GLC_DT_F32) return launch_gqa_t<float, true>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, ctx_gs);   // split-f16 units
+    if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window);
+    if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window);
+    if (dtype == GLC_DT_F32) return launch_gqa_t<float, true>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, ctx_gs, window);   // split-f16 units
     return "attention_gqa_mfma: bad dtype";
 }

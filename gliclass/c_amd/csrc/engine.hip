@@ -114,8 +114,9 @@ struct glc_engine {
     // weights
     void* emb = nullptr; float *eln_g = nullptr, *eln_b = nullptr;
     std::vector<LayerW> layers;
-    std::vector<DecLayerW> dlayers; float* final_norm = nullptr;      // decoder backbone
-    std::map<int, float*> ropes;                                      // Sp -> [Sp][d/2][cos,sin]
+    std::vector<DecLayerW> dlayers; float* final_norm = nullptr;      // decoder backbone; ModernBERT: Wgu = Wi, Wd = mlp.Wo, ln1 / ln2 = attn_norm / mlp_norm
+    float* zero_bias = nullptr;                                       // ModernBERT: [H] zeros, the beta of its bias-free LayerNorms
+    std::map<std::pair<int, float>, float*> ropes;                    // (Sp, theta) -> [Sp][d/2][cos,sin]
     void *QKV = nullptr, *GU = nullptr, *X2 = nullptr;                // decoder workspace: fused QKV rows, [gate|up] rows, second residual buffer
     bool fused_swiglu = false;                                        // Wgu rows interleaved 16 gate / 16 up: SwiGLU runs in the GEMM epilogue
     float* headw[8] = {nullptr};
@@ -232,7 +233,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     }
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     const size_t es = esize(e->dtype);
-    const bool dec = c.backbone == GLC_BACKBONE_DECODER;
+    const bool dec = c.backbone == GLC_BACKBONE_DECODER || c.backbone == GLC_BACKBONE_MODERNBERT;    // (same workspace)
     if (Mpad > e->capM && dec) {
         const size_t nqd = (size_t)c.heads * c.head_dim, nkvd = (size_t)c.kv_heads * c.head_dim;
         void** bufs[] = {&e->X, &e->X2, &e->H1};
@@ -300,13 +301,16 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
         e->capHeadRows = hr;
     }
     if (dec) {
-        if (!e->ropes.count(Sp)) {
+        // one cos / sin table per (Sp, theta): ModernBERT's global and local layers use two bases
+        const float thetas[2] = {c.rope_theta, c.backbone == GLC_BACKBONE_MODERNBERT ? c.rope_theta_local : c.rope_theta};
+        for (float theta : thetas) {
+            if (e->ropes.count({Sp, theta})) continue;
             // Q2:86 inv_freq = 1 / base^(arange(0,d,2)/d) in float32; Q2:97-100 freqs = inv_freq * position, then cos / sin
             const int hd2 = c.head_dim / 2;
             std::vector<float> t((size_t)Sp * hd2 * 2);
             for (int s = 0; s < Sp; ++s)
                 for (int i = 0; i < hd2; ++i) {
-                    const float inv = 1.0f / powf(c.rope_theta, (float)(2 * i) / (float)c.head_dim);
+                    const float inv = 1.0f / powf(theta, (float)(2 * i) / (float)c.head_dim);
                     const float f = inv * (float)s;
                     t[((size_t)s * hd2 + i) * 2] = cosf(f);
                     t[((size_t)s * hd2 + i) * 2 + 1] = sinf(f);
@@ -314,7 +318,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
             float* d = (float*)dmalloc(e, t.size() * sizeof(float), false);
             if (!d) return false;
             if (hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_err("rope table upload failed"); return false; }
-            e->ropes[Sp] = d;
+            e->ropes[{Sp, theta}] = d;
         }
         return true;
     }
@@ -633,14 +637,14 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
         const bool perm = mx && w.bqkv_p;            // Wqkvf_x rows in the RoPE-epilogue order
         if (perm) { g.bias = w.bqkv_p; g.perm_cols = (nq + nkv) * d; }
         const bool rope_epi = perm && mxa;           // Q2:206-211 in one launch: projection, RoPE, scale, MX tiles (gemm256x.hip EPI_QKVR)
-        if (rope_epi) { g.rope_cs = e->ropes[Sp]; g.qscale = qscale; g.nq = nq; g.nkv = nkv; g.Sp = Sp; g.Mvalid = M; g.Qh = e->Qh; g.Kh = e->Kh; g.Vt = e->Vt; }
+        if (rope_epi) { g.rope_cs = e->ropes[{Sp, c.rope_theta}]; g.qscale = qscale; g.nq = nq; g.nkv = nkv; g.Sp = Sp; g.Mvalid = M; g.Qh = e->Qh; g.Kh = e->Kh; g.Vt = e->Vt; }
         { Prof p(e, PC_QKV);
           if (rope_epi) KCHK(gemm_gs(EPI_QKVR, g), false);
           else {
           KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);        // Q2:206-208
-          if (mxa) KCHK(glc_launch_qkv_layout_mx(st, e->QKV, e->ropes[Sp], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale), false);     // Q2:211 RoPE, MX tiles (decoder_mx.hip)
-          else if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, e->ropes[Sp], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale), false);   // Q2:211 RoPE
-          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, e->ropes[Sp], M, Sp, nq, nkv, d, qscale), false); } }
+          if (mxa) KCHK(glc_launch_qkv_layout_mx(st, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale), false);     // Q2:211 RoPE, MX tiles (decoder_mx.hip)
+          else if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale), false);   // Q2:211 RoPE
+          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], M, Sp, nq, nkv, d, qscale), false); } }
         { Prof p(e, PC_ATTN);
           if (mxa) KCHK(glc_launch_attention_gqa_mx(st, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal), false);
           else if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal, mx ? 2 : (gs ? 1 : 0)), false);
@@ -695,9 +699,109 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
     return true;
 }
 
+// ModernBERT backbone (transformers models/modernbert/modeling_modernbert.py, cited as MB:<line>): one launch sequence per batch.
+// Pre-norm residual stream X (operand type T; plain fp32 rows in the fp32 mode), bias-free LayerNorms (beta = e->zero_bias),
+// bidirectional attention with RoPE, the local layers on the windowed attention kernels, GeGLU.  The MX pipeline is not built for
+// this backbone; the fp32 mode's group-split pipeline runs with the norms as kernels of their own (no fold).
+bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, nh = c.heads, d = c.head_dim, L = c.layers;
+    const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
+    hipStream_t st = e->stream;
+    const int dt = e->dtype;
+    const size_t es = esize(dt);
+    const int ccap = e->capC > 0 ? e->capC : 1;
+    if (e->profile) { e->ev_used = 0; }
+    if (e->keep_hidden) {
+        const size_t need = (size_t)(L + 1) * M * H * es;
+        if (need > e->hidden_cap) { dfree(e, e->hidden_dump); e->hidden_dump = dmalloc(e, need); if (!e->hidden_dump) return false; e->hidden_cap = need; }
+    }
+    { Prof p(e, PC_SCAN);
+      KCHK(glc_launch_scan_rows(st, ids, mask, B, S, c.class_token_index, c.embed_class_token, e->klen, e->kfirst, e->cls_pos, e->cls_cnt, ccap), false); }
+    void *X = e->X, *Xn = e->X2;
+    { Prof p(e, PC_EMBED);                                                                                                   // MB:52-71
+      KCHK(glc_launch_embed_plain(st, dt, ids, mask, e->emb, Xn, e->kbias, B, S, Sp, H, c.vocab, c.pad_id), false);
+      KCHK(glc_launch_layernorm(st, dt, Xn, X, e->eln_g, e->zero_bias, c.ln_eps, M, H), false); }
+    if (e->keep_hidden) HIPCHK(hipMemcpyAsync(e->hidden_dump, X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+    const float qscale = 1.4426950408889634f / sqrtf((float)d);         // head_dim^-1/2, times log2(e) for the exp2 softmax
+    const bool mfma = (dt != GLC_F32 || e->dec_split) && e->attn_impl != 1;
+    // group-split pipeline of the fp32 mode (as the decoder's, without the norm fold): LayerNorm / context / GeGLU rows are written as
+    // [32 hi | 32 lo] groups, every projection runs on the 256-tile LDS-DMA kernel; X, QKV and the [input | gate] rows stay plain fp32
+    bool gs = false;
+    if (dt == GLC_F32 && e->gs_mode > 0 && e->w_presplit && e->dec_split && mfma && !e->keep_hidden && H % 256 == 0 && (2 * I) % 256 == 0 &&
+        (3 * H) % 256 == 0 && I % 32 == 0) {
+        GemmArgs t; t.Mpad = Mpad; t.N = H; t.K = H;
+        gs = e->gs_mode == 2 || !glc_gemm_small_m(t);
+    }
+    e->last_gs = gs;
+    e->last_lnf = false; e->last_mx = false; e->last_mx_attn = false;
+    auto norm = [&](const void* src, const float* gamma) -> const char* {      // H1 = LN(src) (group-split rows in the gs pipeline)
+        return gs ? glc_launch_layernorm_gs(st, (const float*)src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H)
+                  : glc_launch_layernorm(st, dt, src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H);
+    };
+    for (int l = 0; l < L; ++l) {
+        const DecLayerW& w = e->dlayers[l];
+        const bool glob = c.local_window <= 0 || l % (c.global_every > 0 ? c.global_every : 1) == 0;
+        const int win = glob ? 0 : c.local_window;
+        float* cs = e->ropes[{Sp, glob ? c.rope_theta : c.rope_theta_local}];
+        // MB:326-331: attn_norm is the identity on layer 0 (the QKV projection reads the embedding norm's rows; as group-split rows in the
+        // gs pipeline, where the same norm runs once more into H1)
+        if (l > 0) { Prof p(e, PC_LN); KCHK(norm(X, w.ln1), false); }
+        else if (gs) { Prof p(e, PC_LN); KCHK(glc_launch_layernorm_gs(st, (const float*)Xn, e->H1, e->eln_g, e->zero_bias, c.ln_eps, M, H), false); }
+        GemmArgs g;
+        g.A = (l == 0 && !gs) ? X : e->H1; g.W = w.Wqkv; g.bias = nullptr; g.C = e->QKV; g.Mpad = Mpad; g.N = 3 * H; g.K = H; g.gs_c_plain = 1;
+        { Prof p(e, PC_QKV);
+          KCHK(gs ? glc_launch_gemm256s_gs(st, EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                  // MB:274-279
+          if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);   // MB:281-282 RoPE
+          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, cs, M, Sp, nh, nh, d, qscale), false); }
+        { Prof p(e, PC_ATTN);                                                                                                // MB:284-297
+          if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, gs ? 1 : 0, win), false);
+          else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nh, nh, d, 0, win), false); }
+        GemmArgs o;
+        o.A = e->CTX; o.W = w.Wo; o.bias = nullptr; o.C = Xn; o.resid = X; o.Mpad = Mpad; o.N = H; o.K = H; o.gs_resid_plain = 1;
+        { Prof p(e, PC_ATTN_OUT); KCHK(gs ? glc_launch_gemm256s_gs(st, EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }   // MB:299, :332
+        std::swap(X, Xn);
+        { Prof p(e, PC_LN); KCHK(norm(X, w.ln2), false); }                                                                  // MB:333
+        const bool need_gu = !(e->fused_swiglu && (gs || dt != GLC_F32));
+        if (need_gu && e->capGU < Mpad) {
+            dfree(e, e->GU); e->GU = dmalloc(e, (size_t)Mpad * 2 * I * es);
+            if (!e->GU) return false;
+            e->capGU = Mpad;
+        }
+        GemmArgs f1;
+        f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.C = e->GU; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
+        { Prof p(e, PC_FFN1);                                                                                                // MB:89-91 gelu(input) * gate
+          if (e->fused_swiglu && gs) { f1.C = e->FF; KCHK(glc_launch_gemm256s_gs(st, EPI_GEGLU, f1), false); }
+          else if (e->fused_swiglu && dt == GLC_F32) {      // small forward of the fp32 mode: plain rows, interleaved [input | gate] columns
+              KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glc_launch_geglu(st, dt, e->GU, e->FF, (size_t)M, I, 1), false); }
+          else if (e->fused_swiglu) { f1.C = e->FF; KCHK(glc_launch_gemm256s(st, dt, EPI_GEGLU, f1), false); }
+          else if (gs) { f1.gs_c_plain = 1; KCHK(glc_launch_gemm256s_gs(st, EPI_BIAS, f1), false); KCHK(glc_launch_geglu_gs(st, (const float*)e->GU, e->FF, (size_t)M, I), false); }
+          else { KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glc_launch_geglu(st, dt, e->GU, e->FF, (size_t)M, I), false); } }
+        GemmArgs f2;
+        f2.A = e->FF; f2.W = w.Wd; f2.bias = nullptr; f2.C = Xn; f2.resid = X; f2.Mpad = Mpad; f2.N = H; f2.K = I; f2.gs_resid_plain = 1;
+        { Prof p(e, PC_FFN2); KCHK(gs ? glc_launch_gemm256s_gs(st, EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }
+        std::swap(X, Xn);
+        if (e->keep_hidden && l + 1 < L)
+            HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)(l + 1) * M * H * es, X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+    }
+    { Prof p(e, PC_LN); KCHK(glc_launch_layernorm(st, dt, X, e->H1, e->final_norm, e->zero_bias, c.ln_eps, M, H), false); }   // MB:476
+    if (e->keep_hidden) HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)L * M * H * es, e->H1, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+    if (C > 0) {
+        Prof p(e, PC_HEAD);
+        float* Gc = e->Gt + (size_t)round_up(B, 128) * H;
+        KCHK(glc_launch_head_gather(st, dt, e->H1, e->cls_pos, ccap, e->Gt, Gc, B, Sp, H, C, c.pooling == GLC_POOL_LAST ? e->klen : nullptr), false);
+        if (c.pooling == GLC_POOL_AVG) KCHK(glc_launch_pool_avg(st, dt, e->H1, e->kbias, e->Gt, B, Sp, H), false);
+        if (!run_head_tail(e, B, C, d_logits)) return false;
+    }
+    HIPCHK(hipGetLastError(), false);
+    e->lastB = B; e->lastS = S; e->lastSp = Sp;
+    return true;
+}
+
 // The launch sequence for one batch.  ids/mask are device pointers.
 bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
     if (e->cfg.backbone == GLC_BACKBONE_DECODER) return run_forward_decoder(e, ids, mask, B, S, C, d_logits);
+    if (e->cfg.backbone == GLC_BACKBONE_MODERNBERT) return run_forward_modernbert(e, ids, mask, B, S, C, d_logits);
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, I = c.inter, nh = c.heads;
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
@@ -991,6 +1095,85 @@ bool create_decoder(glc_engine* e, const float* const* tensors) {
     return ok;
 }
 
+// ModernBERT backbone: upload + convert weights (include/gliclass_hip.h tensor order).  Per layer: Wqkv as it is (rows Q | K | V), Wo,
+// Wi (rows input | gate; interleaved 16 input / 16 gate rows when GeGLU runs in the GEMM epilogue, as the decoder's gate / up), mlp.Wo.
+bool create_modernbert(glc_engine* e, const float* const* tensors) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, L = c.layers;
+    const size_t es = esize(e->dtype);
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return false; }
+    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { set_err("event create failed"); return false; }
+    size_t stage_n = (size_t)c.vocab * H;
+    if (3 * (size_t)H * H > stage_n) stage_n = 3 * (size_t)H * H;
+    if (2 * (size_t)I * H > stage_n) stage_n = 2 * (size_t)I * H;
+    float* staging = nullptr;
+    if (hipMalloc((void**)&staging, stage_n * sizeof(float)) != hipSuccess) { set_err("staging alloc failed"); return false; }
+    bool ok = false;
+    do {
+        e->emb = dmalloc(e, (size_t)c.vocab * H * es, false);
+        if (!e->emb || !upload_as(e, tensors[0], (size_t)c.vocab * H, e->emb, staging)) break;
+        e->eln_g = upload_f32(e, tensors[1], H);
+        e->zero_bias = (float*)dmalloc(e, (size_t)H * sizeof(float));
+        if (!e->eln_g || !e->zero_bias) break;
+        e->dlayers.resize(L);
+        // GeGLU in the epilogue of the staggered 256-tile GEMM when the shapes allow it (16-bit operands; fp32 mode: the group-split GEMM)
+        e->fused_swiglu = (e->dtype != GLC_F32 || (e->w_presplit && e->dec_split && H % 256 == 0)) && (2 * I) % 256 == 0 && H % 32 == 0 && I % 16 == 0 &&
+                          glc_dev_env("GLC_NO_FUSED_SWIGLU") == nullptr;
+        std::vector<float> wi_host(e->fused_swiglu ? 2 * (size_t)I * H : 0);
+        bool lok = true;
+        for (int l = 0; l < L && lok; ++l) {
+            const float* const* t = tensors + glc_mb_layer_base(l);
+            const float* attn_norm = l > 0 ? t[0] : nullptr;
+            if (l > 0) ++t;                                          // t: Wqkv Wo mlp_norm Wi Wo
+            DecLayerW& w = e->dlayers[l];
+            w.Wqkv = dmalloc(e, 3 * (size_t)H * H * es, false);
+            w.Wo = dmalloc(e, (size_t)H * H * es, false);
+            w.Wgu = dmalloc(e, 2 * (size_t)I * H * es, false);
+            w.Wd = dmalloc(e, (size_t)H * I * es, false);
+            if (!w.Wqkv || !w.Wo || !w.Wgu || !w.Wd) { lok = false; break; }
+            lok = upload_as(e, t[0], 3 * (size_t)H * H, w.Wqkv, staging) && upload_as(e, t[1], (size_t)H * H, w.Wo, staging) &&
+                  upload_as(e, t[4], (size_t)H * I, w.Wd, staging);
+            if (lok && e->fused_swiglu) {
+                // rows [32 f, 32 f + 16) = input rows of features 16 f .. 16 f + 15, rows [32 f + 16, 32 f + 32) = their gate rows
+                for (int f = 0; f < I / 16; ++f) {
+                    memcpy(wi_host.data() + (size_t)(32 * f) * H, t[3] + (size_t)(16 * f) * H, (size_t)16 * H * sizeof(float));
+                    memcpy(wi_host.data() + (size_t)(32 * f + 16) * H, t[3] + (size_t)(I + 16 * f) * H, (size_t)16 * H * sizeof(float));
+                }
+                lok = upload_as(e, wi_host.data(), 2 * (size_t)I * H, w.Wgu, staging);
+            } else if (lok) {
+                lok = upload_as(e, t[3], 2 * (size_t)I * H, w.Wgu, staging);
+            }
+            if (!lok) break;
+            if (e->w_presplit && e->dtype == GLC_F32) {     // group-split weight rows (the operand image of both split-f16 GEMM kernels)
+                const char* pm = glc_launch_presplit(e->stream, w.Wqkv, 3 * (size_t)H * H);
+                if (!pm) pm = glc_launch_presplit(e->stream, w.Wo, (size_t)H * H);
+                if (!pm) pm = glc_launch_presplit(e->stream, w.Wgu, 2 * (size_t)I * H);
+                if (!pm) pm = glc_launch_presplit(e->stream, w.Wd, (size_t)H * I);
+                if (pm) { set_err(pm); lok = false; break; }
+            }
+            if (attn_norm) { w.ln1 = upload_f32(e, attn_norm, H); if (!w.ln1) { lok = false; break; } }
+            w.ln2 = upload_f32(e, t[2], H);
+            if (!w.ln2) { lok = false; break; }
+        }
+        if (!lok) break;
+        const int fin = L > 0 ? glc_mb_layer_base(L) : 2;
+        e->final_norm = upload_f32(e, tensors[fin], H);
+        if (!e->final_norm) break;
+        const float* const* ht = tensors + fin + 1;
+        bool hok = true;
+        for (int i = 0; i < 8 && hok; ++i) {
+            e->headw[i] = upload_f32(e, ht[i], (i % 2 == 0) ? (size_t)H * H : (size_t)H); hok = e->headw[i] != nullptr;
+            if (hok && (i % 2 == 0) && e->w_presplit) { const char* pm = glc_launch_presplit(e->stream, e->headw[i], (size_t)H * H); if (pm) { set_err(pm); hok = false; } }
+        }
+        hok = hok && upload_scorer(e, ht + GLC_TENSORS_HEAD);
+        if (!hok) break;
+        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); break; }
+        ok = true;
+    } while (0);
+    (void)hipFree(staging);
+    return ok;
+}
+
 // the value a 16-bit MFMA operand carries for f (host side of glc_launch_convert)
 inline float round_as_operand(float f, int dtype) {
     if (dtype == GLC_F16) return (float)(_Float16)f;
@@ -1041,14 +1224,19 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (dtype != GLC_F32 && dtype != GLC_BF16 && dtype != GLC_F16) { set_err("engine_create: bad dtype"); return nullptr; }
     if (n_tensors != glc_num_tensors_cfg(cfg)) { set_err("engine_create: wrong tensor count"); return nullptr; }
     for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { set_err("engine_create: null tensor"); return nullptr; }
-    const bool dec = cfg->backbone == GLC_BACKBONE_DECODER;
-    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec) { set_err("engine_create: unknown backbone"); return nullptr; }
-    if (!dec && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
+    const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT;
+    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb) { set_err("engine_create: unknown backbone"); return nullptr; }
+    if (mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64 || cfg->local_window < 0 || (cfg->local_window > 0 && cfg->global_every < 1) ||
+               cfg->rope_theta <= 1.f || (cfg->local_window > 0 && cfg->rope_theta_local <= 1.f))) {
+        set_err("engine_create: ModernBERT backbone needs head_dim 64, local_window >= 0, global_every >= 1 and RoPE bases > 1"); return nullptr;
+    }
+    if (!dec && !mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
     if (dec && ((cfg->head_dim != 64 && cfg->head_dim != 128) || cfg->heads <= 0 || cfg->kv_heads < 0 ||
                 cfg->heads % (cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads) || cfg->rope_theta <= 1.f)) {
         set_err("engine_create: decoder backbone needs head_dim 64 or 128, heads % kv_heads == 0 and rope_theta > 1"); return nullptr;
     }
-    if (cfg->hidden % 128 || cfg->inter % 128) { set_err("engine_create: hidden and intermediate sizes must be multiples of 128"); return nullptr; }
+    // (ModernBERT: the GeGLU width may be a multiple of 64 — modernbert-large's 2624 — the fused [input | gate] projection is 2I wide)
+    if (cfg->hidden % 128 || cfg->inter % (mb ? 64 : 128)) { set_err("engine_create: hidden and intermediate sizes must be multiples of 128 (ModernBERT: 64)"); return nullptr; }
     if (cfg->pooling < GLC_POOL_FIRST || cfg->pooling > GLC_POOL_LAST || cfg->scorer < GLC_SCORER_DOT || cfg->scorer > GLC_SCORER_MLP) {
         set_err("engine_create: pooling must be 'first', 'avg' or 'last' and the scorer 'simple', 'weighted-dot' or 'mlp'"); return nullptr;
     }
@@ -1062,8 +1250,8 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (e->cfg.kv_heads <= 0) e->cfg.kv_heads = e->cfg.heads;
     if (const char* pv = getenv("GLICLASS_PRUNE_LAST")) e->prune_last = atoi(pv) != 0;
     { const char* gv = getenv("GLICLASS_F32_GEMM"); e->w_presplit = !(gv && !strcmp(gv, "native")) ; }   // hidden and inter are multiples of 128 (checked above)
-    { const char* av = getenv("GLICLASS_F32_ATTN"); e->dec_split = dtype == GLC_F32 && cfg->backbone == GLC_BACKBONE_DECODER && !(av && !strcmp(av, "native")); }
-    { const char* av = getenv("GLICLASS_F32_ATTN"); e->attn_split = dtype == GLC_F32 && cfg->backbone != GLC_BACKBONE_DECODER && !(av && !strcmp(av, "native")); }
+    { const char* av = getenv("GLICLASS_F32_ATTN"); e->dec_split = dtype == GLC_F32 && (dec || mb) && !(av && !strcmp(av, "native")); }
+    { const char* av = getenv("GLICLASS_F32_ATTN"); e->attn_split = dtype == GLC_F32 && cfg->backbone == GLC_BACKBONE_DEBERTA && !(av && !strcmp(av, "native")); }
     if (const char* lv = glc_dev_env("GLC_LNF")) e->ln_fused = atoi(lv) != 0;      // developer A/B switch
     // MX cross-term pipeline (docs/LOG_r01-r05.md §3e) — the default arithmetic of the large forwards of the default mode since round 3: the
     // projections of the full layers run a_hi*w_hi in f16 MFMAs and both cross terms in one block-scaled fp8 MFMA (per-label
@@ -1073,7 +1261,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
         const char* mv = getenv("GLICLASS_MX");
         const bool eligible = dec ? (dtype == GLC_F32 && e->w_presplit && e->dec_split && e->ln_fused && cfg->hidden % 256 == 0 && (2 * cfg->inter) % 256 == 0 && cfg->inter % 32 == 0)
                                   : (dtype == GLC_F32 && e->w_presplit && e->attn_split && e->ln_fused && cfg->hidden % 256 == 0 && cfg->inter % 256 == 0 && cfg->layers >= 2);
-        e->mx_built = eligible && !(mv && !strcmp(mv, "0"));
+        e->mx_built = eligible && !mb && !(mv && !strcmp(mv, "0"));      // (no MX pipeline for the ModernBERT backbone)
         e->mx = e->mx_built && !(mv && !strcmp(mv, "build"));
         if (const char* av = glc_dev_env("GLC_MX_ATTN")) e->mx_attn = atoi(av) != 0;      // developer A/B switch
         if (const char* av = glc_dev_env("GLC_DEC_ROPE_EPI")) e->dec_rope_epi = atoi(av) != 0;      // developer A/B switch
@@ -1083,6 +1271,10 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (const char* bv = getenv("GLICLASS_LENGTH_BUCKETS")) { const int g = atoi(bv); e->max_buckets = g < 1 ? 1 : (g > 64 ? 64 : g); }
     if (dec) {
         if (!create_decoder(e, tensors)) { glc_engine_destroy(e); return nullptr; }
+        return e;
+    }
+    if (mb) {
+        if (!create_modernbert(e, tensors)) { glc_engine_destroy(e); return nullptr; }
         return e;
     }
     const int H = cfg->hidden, I = cfg->inter, L = cfg->layers, nh = cfg->heads;

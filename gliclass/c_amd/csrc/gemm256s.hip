@@ -373,7 +373,8 @@ __global__ __launch_bounds__(512, 2) void gemm256s_kernel(GemmArgs p, int n_tile
     const float* __restrict__ bias = p.bias;
     float* stg = reinterpret_cast<float*>(smem256 + wave * EPI_PATCH);
     const int qkv_b0 = (EPI == EPI_QKV) ? m0 / p.Sp : 0;
-    if constexpr (EPI == EPI_SWIGLU) {
+    if constexpr (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) {
+        // (EPI_GEGLU, ModernBERT: the same with [input | gate] in place of [gate | up] and gelu(input) * gate, the erf GELU of EPI_GELU)
         // W rows alternate 16 gate features / 16 up features (engine.hip interleaves them at load), so the accumulator
         // blocks j = 0,2 hold gate and j = 1,3 the matching up columns of the SAME 16 features: the product needs no
         // exchange.  The wave's 128x64 sub-tile becomes 128x32 outputs (Q2:47 silu(gate(x)) * up(x)); patch [32 rows][32
@@ -391,9 +392,16 @@ __global__ __launch_bounds__(512, 2) void gemm256s_kernel(GemmArgs p, int n_tile
                     f32x4 gt = acc[2 * c + ii][2 * jj], up = acc[2 * c + ii][2 * jj + 1];
                     if (lnf) { gt *= rs; up *= rs; }
                     f32x4 v;
+                    if constexpr (EPI == EPI_GEGLU) {
+                        f32x2 g0, g1;
+                        if constexpr (GS) { g0 = glc_gelu2_f32((f32x2){gt[0], gt[1]}); g1 = glc_gelu2_f32((f32x2){gt[2], gt[3]}); }
+                        else { g0 = glc_gelu2((f32x2){gt[0], gt[1]}); g1 = glc_gelu2((f32x2){gt[2], gt[3]}); }
+                        v[0] = g0[0] * up[0]; v[1] = g0[1] * up[1]; v[2] = g1[0] * up[2]; v[3] = g1[1] * up[3];
+                    } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        v[r] = gt[r] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * gt[r])) * up[r];
+                        for (int r = 0; r < 4; ++r)
+                            v[r] = gt[r] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * gt[r])) * up[r];
+                    }
                     *reinterpret_cast<f32x4*>(stg + (ii * 16 + r16) * 36 + jj * 16 + 4 * g) = v;
                 }
             }
@@ -718,6 +726,7 @@ template <typename T> const char* launch_t(hipStream_t st, int epi, const GemmAr
         case EPI_GELU: return launch_e<T, EPI_GELU, false>(st, a, 0, ntn);
         case EPI_RESID: return launch_e<T, EPI_RESID, false>(st, a, 0, ntn);
         case EPI_SWIGLU: return launch_e<T, EPI_SWIGLU, false>(st, a, 0, ntn);
+        case EPI_GEGLU: return launch_e<T, EPI_GEGLU, false>(st, a, 0, ntn);
         case EPI_QKV: {   // Q|K columns in row orientation, V columns transposed: two grids, one stream
             const int nqk = 2 * a.H / TN, nq = a.qkv_skip_q ? a.H / TN : 0;     // skip the Q columns when asked
             const char* m = launch_e<T, EPI_QKV, false>(st, a, nq, nqk - nq);
@@ -737,7 +746,7 @@ static bool gemm256s_supported(int dtype, const GemmArgs& a) {
 bool glc_gemm256s_gs_supported(const GemmArgs& a, int epi) {
     if (!(a.Mpad > 0 && a.Mpad % TM == 0 && a.N > 0 && a.N % TN == 0 && a.K > 0 && a.K % 32 == 0)) return false;
     if (epi == EPI_QKV) return a.H % 256 == 0 && a.N == 3 * a.H && a.Sp % 64 == 0 && a.Sp >= 64 && a.nh * 64 == a.H;
-    return epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESID || epi == EPI_SWIGLU;
+    return epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESID || epi == EPI_SWIGLU || epi == EPI_GEGLU;
 }
 
 // fp32 mode on group-split operands (see the kernel header): T = f16 halves, 2K/32 ring stages for 3K/32 MFMA steps.
@@ -753,6 +762,7 @@ const char* glc_launch_gemm256s_gs(hipStream_t st, int epi, const GemmArgs& a) {
         case EPI_GELU: return launch_e<f16_t, EPI_GELU, false, true>(st, a, 0, ntn);
         case EPI_RESID: return launch_e<f16_t, EPI_RESID, false, true>(st, a, 0, ntn);
         case EPI_SWIGLU: return a.bias ? "gemm256s(gs): the SwiGLU epilogue takes no bias" : launch_e<f16_t, EPI_SWIGLU, false, true>(st, a, 0, ntn);
+        case EPI_GEGLU: return a.bias || a.a_stats ? "gemm256s(gs): the GeGLU epilogue takes no bias and no folded norm" : launch_e<f16_t, EPI_GEGLU, false, true>(st, a, 0, ntn);
         case EPI_QKV: {
             const int nqk = 2 * a.H / TN, nq = a.qkv_skip_q ? a.H / TN : 0;
             const char* m = launch_e<f16_t, EPI_QKV, false, true>(st, a, nq, nqk - nq);
@@ -772,7 +782,7 @@ const char* glc_launch_gemm256s(hipStream_t st, int dtype, int epi, const GemmAr
         if (a.H % 256 || a.N != 3 * a.H || a.Sp % 64 || a.Sp < 64 || !a.Qh || !a.Kh || !a.Vt || a.nh * 64 != a.H) return "gemm256s: bad QKV epilogue shape";
     } else if (!a.C) return "gemm256s: null output";
     if (epi == EPI_RESID && !a.resid) return "gemm256s: null residual";
-    if (epi == EPI_SWIGLU && a.bias) return "gemm256s: the SwiGLU epilogue takes no bias";
+    if ((epi == EPI_SWIGLU || epi == EPI_GEGLU) && a.bias) return "gemm256s: the GLU epilogues take no bias";
     return dtype == GLC_DT_BF16 ? launch_t<bf16_t>(st, epi, a) : launch_t<f16_t>(st, epi, a);
 }
 

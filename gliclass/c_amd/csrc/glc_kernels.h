@@ -8,7 +8,8 @@
 enum { GLC_DT_F32 = 0, GLC_DT_BF16 = 1, GLC_DT_F16 = 2 };  // == GLC_F32/BF16/F16 of gliclass_hip.h
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_QKV = 3,
        EPI_SWIGLU = 4,     // gemm256s / gemm256x: W rows interleave 16 gate / 16 up features; C [Mpad, N/2] = silu(gate) * up
-       EPI_QKVR = 5 };     // gemm256x only, decoder backbone: RoPE + softmax scale + the MX tiles of decoder_mx.hip written by the epilogue (rope_cs ..)
+       EPI_QKVR = 5,       // gemm256x only, decoder backbone: RoPE + softmax scale + the MX tiles of decoder_mx.hip written by the epilogue (rope_cs ..)
+       EPI_GEGLU = 6 };    // gemm256s only, ModernBERT: W rows interleave 16 input / 16 gate features; C [Mpad, N/2] = gelu(input) * gate
 
 // Developer A/B switches (GLC_* environment variables: kernel variants kept for same-box comparisons, docs/LOG_r01-r05.md §7) are read only by a
 // library built with -DGLC_DEVELOPER (make DEV=1); the product library reads the documented GLICLASS_* knobs and nothing else.
@@ -286,20 +287,24 @@ const char* glc_launch_embed_plain(hipStream_t st, int dtype, const int64_t* ids
 // (glc_launch_rmsnorm_gs: fp32 X in, group-split Y out; glc_launch_swiglu_gs: plain fp32 [gate | up] rows in, group-split F out)
 const char* glc_launch_rmsnorm_gs(hipStream_t st, const float* X, void* Y, const float* w, float eps, int M, int H);
 const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I);
+const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I);       // gelu(GU[m, i]) * GU[m, I + i] (ModernBERT)
 const char* glc_launch_rmsnorm(hipStream_t st, int dtype, const void* X, void* Y, const float* w, float eps, int M, int H);
 // in-place rotate-half RoPE on the Q and K heads of QKV [M, (nq+2nkv) d]; cs = [Sp][d/2][cos,sin]; Q additionally * qscale
 const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale);
 // F[m,i] = silu(GU[m,i]) * GU[m,I+i]
 const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter = 0);   // inter: 16 gate / 16 up interleaved columns
+// F[m,i] = gelu(GU[m,i]) * GU[m,I+i] (ModernBERT's GeGLU on [input | gate]; erf GELU); inter as above
+const char* glc_launch_geglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter = 0);
 // grouped-query attention on the row-major fused QKV (Q pre-scaled by log2e/sqrt(d)); CTX [B*Sp, nq*d]; impl 1 = straightforward
 const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const void* QKV, const float* kbias, const int* klen, void* CTX,
-                                     int B, int Sp, int nq, int nkv, int d, int causal);
+                                     int B, int Sp, int nq, int nkv, int d, int causal, int window = 0);   // window > 0: keys |q - k| <= window only
 // 16-bit MFMA path: RoPE + scale + fragment-major Q / K / V^T (layouts in decoder.hip), then the flash-style kernel
 const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, const float* cs, void* Qf, void* Kf, void* Vt, int B, int Sp,
                                   int nq, int nkv, int d, float qscale);
 // ctx_gs (fp32 mode only): write the context rows in the group-split format
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
-                                          const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0);
+                                          const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0,
+                                          int window = 0);   // window > 0 (head_dim 64, not causal, ctx_gs != 2): keys |q - k| <= window only
 
 // MX pipeline (decoder_mx.hip, round 4): the fused fp32 projection -> RoPE + scale + MX tiles (f16 hi units + fp8 steps, 4 bytes per element),
 // and the grouped-query attention on them (a_hi*b_hi in f16 MFMAs + both cross terms in one block-scaled fp8 MFMA); CTX as GX rows

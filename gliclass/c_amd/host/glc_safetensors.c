@@ -6,7 +6,7 @@
  * config.json and the safetensors header (8-byte little-endian length, JSON {"name": {"dtype","shape","data_offsets"}},
  * raw little-endian tensor data); F32 / F16 / BF16 tensors are widened to fp32.
  *
- * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` state_dict) under any of the prefixes GLiClass checkpoints use;
+ * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `ModernBertModel` state_dict) under any of the prefixes GLiClass checkpoints use;
  * configuration fields follow transformers' DebertaV2Config / Qwen2Config inside `encoder_config`, and the GLiClass
  * fields as restated in SURVEY.md §8a row a12 (class_token_index, text_token_index, pooling_strategy, scorer_type,
  * embed_class_token, normalize_features ...).  The GLiClass field names come from the upstream python package, which
@@ -134,7 +134,54 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
         c->pos_buckets = 0; c->max_rel_pos = 0;
         if (!pool) c->pooling = GLC_POOL_LAST;
         if (c->kv_heads <= 0 || c->heads % c->kv_heads) REJECT("num_key_value_heads does not divide num_attention_heads");
-    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2)", mt);
+    } else if (!strcmp(mt, "modernbert")) {
+        /* transformers models/modernbert: configuration_modernbert.py (both the transformers-5 form with layer_types / rope_parameters
+         * and the older one with global_attn_every_n_layers / global_rope_theta / local_rope_theta) */
+        c->backbone = GLC_BACKBONE_MODERNBERT;
+        c->kv_heads = c->heads; c->causal = 0;
+        c->pos_buckets = 0; c->max_rel_pos = 0;
+        c->ln_eps = (float)jnum(enc, "norm_eps", 1e-5);
+        if (jflag(enc, "attention_bias", 0)) REJECT("attention_bias=true is not implemented");
+        if (jflag(enc, "mlp_bias", 0)) REJECT("mlp_bias=true is not implemented");
+        if (jflag(enc, "norm_bias", 0)) REJECT("norm_bias=true is not implemented");
+        const char* act = jtext(enc, "hidden_activation");
+        if (act && strcmp(act, "gelu")) REJECT("hidden_activation '%s' is not implemented (gelu)", act);
+        if (c->head_dim != 64) REJECT("head_dim %d is not implemented (64)", c->head_dim);
+        const int la = (int)jnum(enc, "local_attention", 128);
+        if (la < 0 || la % 2) REJECT("local_attention %d is not implemented (an even window)", la);
+        c->local_window = la / 2;
+        int every = (int)jnum(enc, "global_attn_every_n_layers", 3);
+        const gj_value* lt = gj_get(enc, "layer_types");
+        if (gj_is(lt, GJ_ARR)) {
+            /* a list of the periodic form: full on l % every == 0, sliding elsewhere; its period is the first sliding layer's distance
+             * to the full layer before it (or "all full") */
+            if ((int)lt->u.arr.n != c->layers) REJECT("layer_types has %zu entries for %d layers", lt->u.arr.n, c->layers);
+            every = c->layers > 0 ? c->layers : 1;
+            for (int l = 0; l < c->layers; ++l) {
+                const gj_value* v = lt->u.arr.items[l];
+                if (!gj_is(v, GJ_STR) || (strcmp(v->u.str.s, "full_attention") && strcmp(v->u.str.s, "sliding_attention")))
+                    REJECT("layer_types[%d] is not 'full_attention' or 'sliding_attention'", l);
+                if (l > 0 && !strcmp(v->u.str.s, "full_attention") && every == c->layers) { every = l; break; }
+            }
+            for (int l = 0; l < c->layers; ++l)
+                if ((strcmp(lt->u.arr.items[l]->u.str.s, "full_attention") == 0) != (l % every == 0))
+                    REJECT("layer_types is not periodic (full attention on every n-th layer from layer 0)");
+        }
+        if (every < 1) REJECT("global_attn_every_n_layers must be positive");
+        c->global_every = every;
+        c->rope_theta = (float)jnum(enc, "global_rope_theta", 160000.0);
+        c->rope_theta_local = (float)jnum(enc, "local_rope_theta", 10000.0);
+        const gj_value* rp = gj_get(enc, "rope_parameters");
+        if (gj_is(rp, GJ_OBJ)) {
+            const gj_value* fa = gj_get(rp, "full_attention");
+            const gj_value* sa = gj_get(rp, "sliding_attention");
+            if (gj_is(fa, GJ_OBJ)) c->rope_theta = (float)jnum(fa, "rope_theta", c->rope_theta);
+            if (gj_is(sa, GJ_OBJ)) c->rope_theta_local = (float)jnum(sa, "rope_theta", c->rope_theta_local);
+            const char* rt = gj_is(fa, GJ_OBJ) ? jtext(fa, "rope_type") : NULL;
+            const char* rs = gj_is(sa, GJ_OBJ) ? jtext(sa, "rope_type") : NULL;
+            if ((rt && strcmp(rt, "default")) || (rs && strcmp(rs, "default"))) REJECT("rope_type other than 'default' is not implemented");
+        }
+    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, modernbert)", mt);
     return 0;
 }
 
@@ -206,7 +253,8 @@ int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
     glc_model_config* c = &w->cfg;
     char found[200];
     /* the embedding matrix decides the vocabulary size (tokens were added after the backbone config was written) */
-    const gj_value* emb = st_find(&st, c->backbone == GLC_BACKBONE_DECODER ? "embed_tokens.weight" : "embeddings.word_embeddings.weight", found, sizeof found);
+    const gj_value* emb = st_find(&st, c->backbone == GLC_BACKBONE_DECODER ? "embed_tokens.weight" :
+                                       c->backbone == GLC_BACKBONE_MODERNBERT ? "embeddings.tok_embeddings.weight" : "embeddings.word_embeddings.weight", found, sizeof found);
     const gj_value* eshape = gj_get(emb, "shape");
     if (!emb || !gj_is(eshape, GJ_ARR) || eshape->u.arr.n != 2) { fprintf(stderr, "Error: '%s': no word-embedding tensor under any known prefix\n", stp); goto done; }
     c->vocab = (int32_t)eshape->u.arr.items[0]->u.num;

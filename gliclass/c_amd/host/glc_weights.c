@@ -73,6 +73,24 @@ int glc_named_config(const char* name, glc_model_config* c) {
             c->ln_eps = 1e-6f; c->logit_scale = 1.0f;
             return 0;
         }
+    /* ModernBERT backbones (config.py CONFIGS "mb-tiny", "mb-mini", "modernbert-base", "modernbert-large") */
+    static const struct { const char* n; int vocab, hidden, layers, heads, inter, window, pooling; } MB[] = {
+        {"mb-tiny", 515, 128, 4, 2, 192, 8, GLC_POOL_FIRST},            {"mb-mini", 1027, 256, 4, 4, 384, 64, GLC_POOL_AVG},
+        {"modernbert-base", 50370, 768, 22, 12, 1152, 64, GLC_POOL_FIRST}, {"modernbert-large", 50370, 1024, 28, 16, 2624, 64, GLC_POOL_FIRST},
+    };
+    for (size_t i = 0; i < sizeof(MB) / sizeof(MB[0]); ++i)
+        if (strcmp(name, MB[i].n) == 0) {
+            memset(c, 0, sizeof(*c));
+            c->vocab = MB[i].vocab; c->hidden = MB[i].hidden; c->layers = MB[i].layers; c->heads = MB[i].heads;
+            c->head_dim = 64; c->inter = MB[i].inter; c->pos_buckets = 256; c->max_rel_pos = 512;
+            c->pad_id = 0; c->cls_id = 1; c->sep_id = 2;
+            c->class_token_index = c->vocab - 2; c->text_token_index = c->vocab - 1;
+            c->pooling = MB[i].pooling; c->scorer = GLC_SCORER_DOT; c->embed_class_token = 1; c->normalize_features = 0;
+            c->backbone = GLC_BACKBONE_MODERNBERT; c->kv_heads = c->heads; c->causal = 0; c->rope_theta = 160000.0f;
+            c->ln_eps = 1e-5f; c->logit_scale = 1.0f;
+            c->local_window = MB[i].window; c->global_every = 3; c->rope_theta_local = 10000.0f;
+            return 0;
+        }
     return -1;
 }
 
@@ -129,6 +147,28 @@ int glc_tensor_spec(const glc_model_config* c, int i, char* name, uint64_t shape
     *mean = 0.0;
 #define SPEC1(nm, n0, a, m) do { snprintf(name, 96, "%s", nm); shape[0] = (n0); *amp = (a); *mean = (m); return 1; } while (0)
 #define SPEC2(nm, n0, n1, a) do { snprintf(name, 96, "%s", nm); shape[0] = (n0); shape[1] = (n1); *amp = (a); return 2; } while (0)
+    if (c->backbone == GLC_BACKBONE_MODERNBERT) {       /* include/gliclass_hip.h; mirrors weights.tensor_specs */
+        char buf[96];
+        if (i == 0) SPEC2("embeddings.tok_embeddings.weight", (uint64_t)c->vocab, H, 1.0);
+        if (i == 1) SPEC1("embeddings.norm.weight", H, 0.2, 1.0);
+        const int nend = c->layers > 0 ? glc_mb_layer_base(c->layers) : 2;      /* index of final_norm */
+        if (i >= 2 && i < nend) {
+            int l = 0;
+            while (l + 1 < c->layers && i >= glc_mb_layer_base(l + 1)) ++l;
+            const int k = i - glc_mb_layer_base(l) + (l == 0 ? 1 : 0);          /* 0 attn_norm (l > 0 only), 1 Wqkv, 2 Wo, 3 mlp_norm, 4 Wi, 5 Wo */
+            static const char* sfx[6] = {"attn_norm.weight", "attn.Wqkv.weight", "attn.Wo.weight", "mlp_norm.weight", "mlp.Wi.weight", "mlp.Wo.weight"};
+            snprintf(buf, sizeof buf, "layers.%d.%s", l, sfx[k]);
+            switch (k) {
+                case 0: case 3: SPEC1(buf, H, 0.2, 1.0);
+                case 1: SPEC2(buf, 3 * H, H, lin_amp(1.6, (double)H));
+                case 2: SPEC2(buf, H, H, lin_amp(0.7, (double)H));
+                case 4: SPEC2(buf, 2 * I, H, lin_amp(1.0, (double)H));
+                default: SPEC2(buf, H, I, lin_amp(0.7, (double)I));
+            }
+        }
+        if (i == nend) SPEC1("final_norm.weight", H, 0.2, 1.0);
+        return head_spec(c, i - nend - 1, name, shape, amp, mean);
+    }
     if (c->backbone == GLC_BACKBONE_DECODER) {
         const uint64_t nqd = (uint64_t)c->heads * (uint64_t)c->head_dim;
         const uint64_t nkvd = (uint64_t)(c->kv_heads > 0 ? c->kv_heads : c->heads) * (uint64_t)c->head_dim;
@@ -263,7 +303,14 @@ static int load_blob(const char* path, glc_weights* w) {
     c->embed_class_token = ints[15]; c->normalize_features = ints[16];
     c->backbone = ints[17]; c->kv_heads = ints[18]; c->causal = ints[19];
     c->ln_eps = fl[0]; c->logit_scale = fl[1]; c->rope_theta = fl[2];
-    if (ver != 2 || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
+    if (ver == 3) {          /* written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
+        int32_t i3[2];
+        float f3;
+        memcpy(i3, b + 16 + sizeof ints + sizeof fl, sizeof i3);
+        memcpy(&f3, b + 16 + sizeof ints + sizeof fl + sizeof i3, sizeof f3);
+        c->local_window = i3[0]; c->global_every = i3[1]; c->rope_theta_local = f3;
+    }
+    if ((ver != 2 && ver != 3) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
         fprintf(stderr, "Error: '%s': unsupported GLCW header (version %u, %u tensors)\n", path, ver, nt);
         return -1;
     }

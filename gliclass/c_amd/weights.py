@@ -16,7 +16,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from .config import GLiClassConfig, BACKBONE_DECODER, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
+from .config import GLiClassConfig, BACKBONE_DECODER, BACKBONE_MODERNBERT, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
 from . import prng
 
 MAGIC = b"GLCW\x00\x01\x00\x00"
@@ -27,6 +27,9 @@ _INT_FIELDS = ["vocab", "hidden", "layers", "heads", "head_dim", "inter", "pos_b
                "pad_id", "cls_id", "sep_id", "class_token_index", "text_token_index",
                "pooling", "scorer", "embed_class_token", "normalize_features", "backbone", "kv_heads", "causal"]
 _F32_FIELDS = ["ln_eps", "logit_scale", "rope_theta"]
+# version 3 (ModernBERT backbone only): + local_window, global_every (int32), rope_theta_local (f32) after the v2 slots
+_V3_INT_FIELDS = ["local_window", "global_every"]
+_V3_F32_FIELDS = ["rope_theta_local"]
 
 
 def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float, float]]:
@@ -68,6 +71,23 @@ def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float,
                 ("scorer.mlp.4.weight", (1, Mh // 2), lin(3.0, Mh // 2), 0.0), ("scorer.mlp.4.bias", (1,), 0.1, 0.0),
             ]
         return out
+
+    if cfg.backbone == BACKBONE_MODERNBERT:
+        # HF ModernBertModel.state_dict() names (prefix-free; no biases).  Wqkv rows: Q | K | V; Wi rows: input | gate.
+        specs = [("embeddings.tok_embeddings.weight", (cfg.vocab, H), 1.0, 0.0), ("embeddings.norm.weight", (H,), 0.2, 1.0)]
+        for i in range(L):
+            p = f"layers.{i}."
+            if i > 0:
+                specs += [(p + "attn_norm.weight", (H,), 0.2, 1.0)]
+            specs += [
+                (p + "attn.Wqkv.weight", (3 * H, H), lin(1.6, H), 0.0),
+                (p + "attn.Wo.weight", (H, H), lin(0.7, H), 0.0),
+                (p + "mlp_norm.weight", (H,), 0.2, 1.0),
+                (p + "mlp.Wi.weight", (2 * I, H), lin(1.0, H), 0.0),
+                (p + "mlp.Wo.weight", (H, I), lin(0.7, I), 0.0),
+            ]
+        specs += [("final_norm.weight", (H,), 0.2, 1.0)]
+        return specs + head_specs()
 
     if cfg.backbone == BACKBONE_DECODER:
         # HF Qwen2Model.state_dict() names (prefix-free).  q/k amplitudes give score std ~ 2-3 after 1/sqrt(d).
@@ -133,9 +153,13 @@ def make_weights(cfg: GLiClassConfig, seed: int = 42) -> Dict[str, np.ndarray]:
 
 def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
     d = cfg.asdict()
-    b = MAGIC + struct.pack("<II", 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
+    v3 = cfg.backbone == BACKBONE_MODERNBERT          # every other backbone keeps writing byte-identical v2 headers
+    b = MAGIC + struct.pack("<II", 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
     b += struct.pack("<%di" % len(_INT_FIELDS), *[int(d[k]) for k in _INT_FIELDS])
     b += struct.pack("<%df" % len(_F32_FIELDS), *[float(d[k]) for k in _F32_FIELDS])
+    if v3:
+        b += struct.pack("<%di" % len(_V3_INT_FIELDS), *[int(d[k]) for k in _V3_INT_FIELDS])
+        b += struct.pack("<%df" % len(_V3_F32_FIELDS), *[float(d[k]) for k in _V3_F32_FIELDS])
     assert len(b) <= HEADER_BYTES
     return b + b"\x00" * (HEADER_BYTES - len(b))
 
@@ -173,12 +197,16 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if hdr[:8] != MAGIC:
         raise ValueError("not a GLCW blob")
     ver, n_t = struct.unpack_from("<II", hdr, 8)
-    if ver != 2:
+    if ver not in (2, 3):
         raise ValueError(f"unsupported GLCW version {ver}")
     ints = struct.unpack_from("<%di" % len(_INT_FIELDS), hdr, 16)
     flts = struct.unpack_from("<%df" % len(_F32_FIELDS), hdr, 16 + 4 * len(_INT_FIELDS))
     kw = dict(zip(_INT_FIELDS, ints))
     kw.update(dict(zip(_F32_FIELDS, flts)))
+    if ver == 3:
+        o3 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS))
+        kw.update(dict(zip(_V3_INT_FIELDS, struct.unpack_from("<%di" % len(_V3_INT_FIELDS), hdr, o3))))
+        kw.update(dict(zip(_V3_F32_FIELDS, struct.unpack_from("<%df" % len(_V3_F32_FIELDS), hdr, o3 + 4 * len(_V3_INT_FIELDS)))))
     cfg = GLiClassConfig(name="blob", **kw)
     tensors = {}
     for i in range(n_t):

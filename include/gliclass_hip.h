@@ -37,7 +37,9 @@ enum { GLC_SCORER_DOT = 0, GLC_SCORER_WEIGHTED_DOT = 1, GLC_SCORER_MLP = 2 };
 #define GLC_SCORER_MLP_HIDDEN 256
 /* backbone family: DeBERTa-v2/v3 disentangled encoder, or a decoder-style stack with Qwen2 arithmetic (RMSNorm, RoPE,
  * grouped-query attention, SwiGLU; SURVEY.md §8a row a16, BASELINE.json configs[4]) */
-enum { GLC_BACKBONE_DEBERTA = 0, GLC_BACKBONE_DECODER = 1 };
+enum { GLC_BACKBONE_DEBERTA = 0, GLC_BACKBONE_DECODER = 1,
+       GLC_BACKBONE_MODERNBERT = 2 /* ModernBERT encoder: LayerNorm without bias, RoPE, bidirectional attention with a sliding window on the
+                                      local layers, GeGLU (transformers models/modernbert/modeling_modernbert.py) */ };
 
 /* Same int/float slots, same order, as the .glcw blob header (gliclass/c_amd/weights.py). */
 typedef struct glc_model_config {
@@ -46,7 +48,11 @@ typedef struct glc_model_config {
     int32_t pooling, scorer, embed_class_token, normalize_features;
     int32_t backbone, kv_heads, causal;    /* decoder backbone: key/value heads (0 = heads), causal mask on/off */
     float ln_eps, logit_scale;             /* ln_eps is rms_norm_eps for the decoder backbone */
-    float rope_theta;
+    float rope_theta;                      /* ModernBERT: the global layers' base */
+    /* ModernBERT: local layers attend to keys with |q - k| <= local_window (0 = every layer global); layer l is global when
+     * l % global_every == 0; rope_theta_local is the local layers' RoPE base */
+    int32_t local_window, global_every;
+    float rope_theta_local;
 } glc_model_config;
 
 /* Tensor order expected in `tensors[]` (all fp32, row-major, nn.Linear weights are [out,in]):
@@ -71,10 +77,21 @@ static inline int glc_num_scorer_tensors(int scorer) { return scorer == GLC_SCOR
  *                        mlp.gate_proj.weight [I,H]  mlp.up_proj.weight [I,H]  mlp.down_proj.weight [H,I]
  *   then norm.weight [H], then the same 8 head tensors */
 #define GLC_DEC_TENSORS_PER_LAYER 12
+/* ModernBERT backbone (names of HF ModernBertModel.state_dict(); no biases anywhere):
+ *   0 embeddings.tok_embeddings.weight [vocab,H]       1 embeddings.norm.weight [H]
+ *   then per layer l: layers.l.attn_norm.weight [H] (only for l > 0; layer 0's is the identity)
+ *                     attn.Wqkv.weight [3H,H] (rows: Q | K | V, head-major)  attn.Wo.weight [H,H]
+ *                     mlp_norm.weight [H]  mlp.Wi.weight [2I,H] (rows: input | gate)  mlp.Wo.weight [H,I]
+ *   then final_norm.weight [H], then the same 8 head tensors */
+#define GLC_MB_TENSORS_PER_LAYER 6
 static inline int glc_num_tensors_cfg(const glc_model_config* c) {
+    if (c->backbone == GLC_BACKBONE_MODERNBERT)
+        return 3 + GLC_MB_TENSORS_PER_LAYER * c->layers - (c->layers > 0 ? 1 : 0) + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     return (c->backbone == GLC_BACKBONE_DECODER ? 2 + GLC_DEC_TENSORS_PER_LAYER * c->layers + GLC_TENSORS_HEAD : glc_num_tensors(c->layers)) +
            glc_num_scorer_tensors(c->scorer);
 }
+/* index of layer l's first tensor (attn_norm for l > 0, Wqkv for l = 0) in the ModernBERT order */
+static inline int glc_mb_layer_base(int l) { return l == 0 ? 2 : 2 + GLC_MB_TENSORS_PER_LAYER * l - 1; }
 
 typedef struct glc_engine glc_engine;
 
