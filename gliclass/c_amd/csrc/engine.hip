@@ -223,6 +223,101 @@ bool init_range_guard(glc_engine* e) {
     e->h_gxsat[0] = e->h_gxsat[1] = 0;
     return true;
 }
+// free a workspace buffer and allocate it again (zeroed) at its new size
+template <class T> bool regrow(glc_engine* e, T*& p, size_t bytes) {
+    dfree(e, p);
+    p = (T*)dmalloc(e, bytes);
+    return p != nullptr;
+}
+// a host table in device memory (hipMemcpy: complete on return)
+template <class T> T* upload_table(glc_engine* e, const std::vector<T>& t, const char* what) {
+    T* d = (T*)dmalloc(e, t.size() * sizeof(T), false);
+    if (!d) return nullptr;
+    if (hipMemcpy(d, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { set_err(std::string(what) + " upload failed"); return nullptr; }
+    return d;
+}
+
+// decoder / ModernBERT: one cos / sin table per (Sp, theta); ModernBERT's global and local layers use two bases
+bool build_rope_tables(glc_engine* e, int Sp) {
+    const glc_model_config& c = e->cfg;
+    const float thetas[2] = {c.rope_theta, c.backbone == GLC_BACKBONE_MODERNBERT ? c.rope_theta_local : c.rope_theta};
+    for (float theta : thetas) {
+        if (e->ropes.count({Sp, theta})) continue;
+        // Q2:86 inv_freq = 1 / base^(arange(0,d,2)/d) in float32; Q2:97-100 freqs = inv_freq * position, then cos / sin
+        const int hd2 = c.head_dim / 2;
+        std::vector<float> t((size_t)Sp * hd2 * 2);
+        for (int s = 0; s < Sp; ++s)
+            for (int i = 0; i < hd2; ++i) {
+                const float inv = 1.0f / powf(theta, (float)(2 * i) / (float)c.head_dim);
+                const float f = inv * (float)s;
+                t[((size_t)s * hd2 + i) * 2] = cosf(f);
+                t[((size_t)s * hd2 + i) * 2 + 1] = sinf(f);
+            }
+        float* d = upload_table(e, t, "rope table");
+        if (!d) return false;
+        e->ropes[{Sp, theta}] = d;
+    }
+    return true;
+}
+
+// DeBERTa: the relative-position tables of one padded length.  dtabs[Sp] guards the whole block, so it is written last: a call that
+// fails part-way leaves no entry and the next forward at this length builds every table again.
+bool build_position_tables(glc_engine* e, int Sp) {
+    if (e->dtabs.count(Sp)) return true;
+    const glc_model_config& c = e->cfg;
+    const size_t es = esize(e->dtype);
+    std::vector<int32_t> t(2 * Sp - 1);
+    glc_delta_table(Sp, c.pos_buckets, c.max_rel_pos, t.data());
+    int32_t* d = upload_table(e, t, "dtab");
+    if (!d) return false;
+    auto dl_of = [&](long long j) { const long long r = j - 64; return t[r < 0 ? 0 : (r > (long long)t.size() - 1 ? t.size() - 1 : (size_t)r)]; };
+    // band-kernel addressing table: entry j <-> relative distance clamp(j - 64, 0, 2Sp-2) - (Sp-1); x = byte offset of PQ row
+    // delta in the Q fragment layout, y = byte offset of PK row delta in the K layout (pi on the row) — glc_layout.h
+    std::vector<int2> o(t.size() + 128);
+    for (size_t j = 0; j < o.size(); ++j) {
+        const int dl = dl_of((long long)j);
+        o[j].x = ((dl >> 5) * 2048 + (dl & 31) * 8) * (int)es;
+        o[j].y = ((dl >> 5) * 2048 + glc_pi32(dl & 31) * 8) * (int)es;
+    }
+    int2* od = upload_table(e, o, "otab");
+    if (!od) return false;
+    e->otabs[Sp] = od;
+    if (es == 4) {
+        // MX band kernel (attention_mx.hip, round 6): the same rows as ready-made load offsets into the PLANAR tile images of the position tables
+        // (glc_layout.h) — per lane half hh and entry j (NE = 2 Sp + 512 entries: 64 clamped ones in front, the rest behind, so that no index the
+        // kernel forms needs a clamp): .x = offset of the PQ row of entry j, .y = offset of the PK row of entry NE - 1 - j (the PK half runs
+        // BACKWARDS: a lane that adds its column c to a wave-uniform base walks the PQ rows up and the PK rows down with the same per-lane
+        // register); offset = tile * 8192 + slot * 16 + hh * 512: the lane's 16 bytes of f16 unit 0; unit s at + s * 1024, MX plane k at + 4096 + k * 1024
+        const int NE = 2 * Sp + 512;
+        std::vector<int2> m((size_t)2 * NE);
+        for (int hh = 0; hh < 2; ++hh)
+            for (int j = 0; j < NE; ++j) {
+                const int dq = dl_of(j), dk = dl_of(NE - 1 - j);
+                m[(size_t)hh * NE + j] = make_int2((dq >> 5) * 8192 + (dq & 31) * 16 + hh * 512, (dk >> 5) * 8192 + glc_pi32(dk & 31) * 16 + hh * 512);
+            }
+        int2* md = upload_table(e, m, "mtab");
+        if (!md) return false;
+        e->mtabs[Sp] = md;
+    }
+    // saturation points of the table: delta == P-1 for every q-k >= rsat_pos, delta == 0 for every q-k <= rsat_neg
+    int rp = Sp, rn = -Sp;
+    for (int r = Sp - 1; r >= -(Sp - 1) && t[r + Sp - 1] == 2 * (c.pos_buckets > 0 ? c.pos_buckets : c.max_rel_pos) - 1; --r) rp = r;
+    for (int r = -(Sp - 1); r <= Sp - 1 && t[r + Sp - 1] == 0; ++r) rn = r;
+    e->dsat[Sp] = std::make_pair(rp, rn);
+    // tables of the bucket-space MX attention (attention_mx2.hip); a table without the structure it needs keeps the band kernel
+    std::vector<unsigned char> idx16;
+    std::vector<int4> tinfo;
+    void* d_idx = nullptr; int4* d_ti = nullptr;
+    if (e->dtype == GLC_F32 && glc_mx2_build_tables(Sp, e->P, t.data(), idx16, tinfo)) {
+        d_idx = upload_table(e, idx16, "mx2 table");
+        d_ti = d_idx ? upload_table(e, tinfo, "mx2 table") : nullptr;
+        if (!d_ti) return false;
+    }
+    e->mx2tabs[Sp] = std::make_pair(d_idx, d_ti);
+    e->dtabs[Sp] = d;
+    return true;
+}
+
 bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     const glc_model_config& c = e->cfg;
     if (!init_range_guard(e)) return false;
@@ -234,168 +329,62 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     const size_t es = esize(e->dtype);
     const bool dec = c.backbone == GLC_BACKBONE_DECODER || c.backbone == GLC_BACKBONE_MODERNBERT;    // (same workspace)
-    if (Mpad > e->capM && dec) {
-        const size_t nqd = (size_t)c.heads * c.head_dim, nkvd = (size_t)c.kv_heads * c.head_dim;
-        void** bufs[] = {&e->X, &e->X2, &e->H1};
-        for (void** b : bufs) { dfree(e, *b); *b = dmalloc(e, (size_t)Mpad * c.hidden * es); if (!*b) return false; }
-        dfree(e, e->QKV); e->QKV = dmalloc(e, (size_t)Mpad * (nqd + 2 * nkvd) * es); if (!e->QKV) return false;
-        dfree(e, e->CTX); e->CTX = dmalloc(e, (size_t)Mpad * nqd * es); if (!e->CTX) return false;
-        if (e->dtype != GLC_F32 || e->dec_split) {          // fragment-major operands of the MFMA attention kernel (fp32 mode: split-f16 units, same bytes)
-            dfree(e, e->Qh); e->Qh = dmalloc(e, (size_t)Mpad * nqd * es); if (!e->Qh) return false;
-            dfree(e, e->Kh); e->Kh = dmalloc(e, (size_t)Mpad * nkvd * es); if (!e->Kh) return false;
-            dfree(e, e->Vt); e->Vt = dmalloc(e, (size_t)Mpad * nkvd * es); if (!e->Vt) return false;
-        }
-        // [gate | up] rows: read only by the launches without the SwiGLU epilogue (unfused builds, the fp32 mode's small forwards) — allocated
-        // by the forward that takes such a launch (need_gu), not for every capacity step (2.3 GB at c5 that the group-split pipeline never touches)
-        dfree(e, e->GU); e->GU = nullptr; e->capGU = 0;
-        dfree(e, e->FF); e->FF = dmalloc(e, (size_t)Mpad * c.inter * es); if (!e->FF) return false;
-        if (e->dtype == GLC_F32) {             // RMSNorm statistics of the two residual-stream buffers + the producers' partials
-            dfree(e, e->statsA); e->statsA = (float2*)dmalloc(e, (size_t)Mpad * sizeof(float2)); if (!e->statsA) return false;
-            dfree(e, e->statsB); e->statsB = (float2*)dmalloc(e, (size_t)Mpad * sizeof(float2)); if (!e->statsB) return false;
-            dfree(e, e->ln_part); e->ln_part = (float2*)dmalloc(e, (size_t)Mpad * ((c.hidden + 63) / 64) * sizeof(float2)); if (!e->ln_part) return false;
-        }
-        dfree(e, e->kbias); e->kbias = (float*)dmalloc(e, (size_t)Mpad * sizeof(float)); if (!e->kbias) return false;
-        e->capM = Mpad;
-        e->hidden_cap = 0;
-    }
     if (Mpad > e->capM) {
-        void** bufs[] = {&e->X, &e->Qh, &e->Kh, &e->Vt, &e->CTX, &e->T1, &e->H1};
-        for (void** b : bufs) { dfree(e, *b); *b = dmalloc(e, (size_t)Mpad * c.hidden * es); if (!*b) return false; }
-        dfree(e, e->FF); e->FF = dmalloc(e, (size_t)Mpad * c.inter * es); if (!e->FF) return false;
-        {                                      // (small; kept whether or not the fold is switched on: glc_debug_set_ln_fused)
-            dfree(e, e->statsA); e->statsA = (float2*)dmalloc(e, (size_t)Mpad * sizeof(float2)); if (!e->statsA) return false;
-            dfree(e, e->statsB); e->statsB = (float2*)dmalloc(e, (size_t)Mpad * sizeof(float2)); if (!e->statsB) return false;
-            dfree(e, e->ln_part); e->ln_part = (float2*)dmalloc(e, (size_t)Mpad * ((c.hidden + 63) / 64) * sizeof(float2)); if (!e->ln_part) return false;
+        const size_t rows_h = (size_t)Mpad * c.hidden * es;
+        if (!regrow(e, e->X, rows_h) || !regrow(e, e->H1, rows_h) || !regrow(e, e->FF, (size_t)Mpad * c.inter * es) ||
+            !regrow(e, e->kbias, (size_t)Mpad * sizeof(float))) return false;
+        // (mean, rstd) or (0, rstd) per row of the two residual-stream buffers + the producers' partials (small; DeBERTa keeps them whether or not
+        // the fold is switched on: glc_debug_set_ln_fused; the decoder's RMSNorm fold exists in the fp32 mode only)
+        if (!dec || e->dtype == GLC_F32) {
+            if (!regrow(e, e->statsA, (size_t)Mpad * sizeof(float2)) || !regrow(e, e->statsB, (size_t)Mpad * sizeof(float2)) ||
+                !regrow(e, e->ln_part, (size_t)Mpad * ((c.hidden + 63) / 64) * sizeof(float2))) return false;
         }
-        dfree(e, e->kbias); e->kbias = (float*)dmalloc(e, (size_t)Mpad * sizeof(float)); if (!e->kbias) return false;
+        if (dec) {
+            const size_t nqd = (size_t)c.heads * c.head_dim, nkvd = (size_t)c.kv_heads * c.head_dim;
+            if (!regrow(e, e->X2, rows_h) || !regrow(e, e->QKV, (size_t)Mpad * (nqd + 2 * nkvd) * es) || !regrow(e, e->CTX, (size_t)Mpad * nqd * es)) return false;
+            if (e->dtype != GLC_F32 || e->dec_split) {          // fragment-major operands of the MFMA attention kernel (fp32 mode: split-f16 units, same bytes)
+                if (!regrow(e, e->Qh, (size_t)Mpad * nqd * es) || !regrow(e, e->Kh, (size_t)Mpad * nkvd * es) || !regrow(e, e->Vt, (size_t)Mpad * nkvd * es)) return false;
+            }
+            // [gate | up] rows: read only by the launches without the SwiGLU epilogue (unfused builds, the fp32 mode's small forwards) — allocated
+            // by the forward that takes such a launch (gated_ffn), not for every capacity step (2.3 GB at c5 that the group-split pipeline never touches)
+            dfree(e, e->GU); e->GU = nullptr; e->capGU = 0;
+        } else {
+            for (void** b : {&e->Qh, &e->Kh, &e->Vt, &e->CTX, &e->T1}) if (!regrow(e, *b, rows_h)) return false;
+        }
         e->capM = Mpad;
         e->hidden_cap = 0;   // dump buffer is re-made lazily
     }
     if (B > e->capB || C > e->capC) {
         const int nb = B > e->capB ? B : e->capB, nc = C > e->capC ? C : e->capC;
-        dfree(e, e->klen); dfree(e, e->kfirst); dfree(e, e->cls_cnt); dfree(e, e->cls_pos); dfree(e, e->d_logits);
-        e->klen = (int*)dmalloc(e, (size_t)nb * sizeof(int));
-        e->kfirst = (int*)dmalloc(e, (size_t)nb * sizeof(int));
-        e->cls_cnt = (int*)dmalloc(e, (size_t)nb * sizeof(int));
-        e->cls_pos = (int*)dmalloc(e, (size_t)nb * (nc > 0 ? nc : 1) * sizeof(int));
-        e->d_logits = (float*)dmalloc(e, (size_t)nb * (nc > 0 ? nc : 1) * sizeof(float));
-        if (!e->klen || !e->kfirst || !e->cls_cnt || !e->cls_pos || !e->d_logits) return false;
+        const size_t nbc = (size_t)nb * (nc > 0 ? nc : 1);
+        if (!regrow(e, e->klen, (size_t)nb * sizeof(int)) || !regrow(e, e->kfirst, (size_t)nb * sizeof(int)) || !regrow(e, e->cls_cnt, (size_t)nb * sizeof(int)) ||
+            !regrow(e, e->cls_pos, nbc * sizeof(int)) || !regrow(e, e->d_logits, nbc * sizeof(float))) return false;
         e->capB = nb; e->capC = nc;
     }
     if (B * S > e->capIds) {
-        dfree(e, e->d_ids); dfree(e, e->d_mask);
-        e->d_ids = (int64_t*)dmalloc(e, (size_t)B * S * sizeof(int64_t));
-        e->d_mask = (int64_t*)dmalloc(e, (size_t)B * S * sizeof(int64_t));
-        if (!e->d_ids || !e->d_mask) return false;
+        if (!regrow(e, e->d_ids, (size_t)B * S * sizeof(int64_t)) || !regrow(e, e->d_mask, (size_t)B * S * sizeof(int64_t))) return false;
         e->capIds = B * S;
     }
     const int hr = round_up(B, 128) + round_up(B * (C > 0 ? C : 1), 128);      // text rows then class rows, each group 128-aligned
     if (hr > e->capHeadRows) {
-        float** bufs[] = {&e->Gt, &e->G1t, &e->G2t};
-        for (float** b : bufs) { dfree(e, *b); *b = (float*)dmalloc(e, (size_t)hr * c.hidden * sizeof(float)); if (!*b) return false; }
-        if (c.scorer != GLC_SCORER_DOT) {      // weighted-dot: [hr, 2H] + [rc, 3H] + [rc, 4H]; mlp: [rc, 2H] + [rc, 256] + [rc, 128] (rc <= hr)
-            dfree(e, e->scorer_ws);
-            e->scorer_ws = (float*)dmalloc(e, (size_t)hr * (9 * (size_t)c.hidden + 2 * GLC_SCORER_MLP_HIDDEN) * sizeof(float));
-            if (!e->scorer_ws) return false;
-        }
+        for (float** b : {&e->Gt, &e->G1t, &e->G2t}) if (!regrow(e, *b, (size_t)hr * c.hidden * sizeof(float))) return false;
+        // weighted-dot: [hr, 2H] + [rc, 3H] + [rc, 4H]; mlp: [rc, 2H] + [rc, 256] + [rc, 128] (rc <= hr)
+        if (c.scorer != GLC_SCORER_DOT && !regrow(e, e->scorer_ws, (size_t)hr * (9 * (size_t)c.hidden + 2 * GLC_SCORER_MLP_HIDDEN) * sizeof(float))) return false;
         e->capHeadRows = hr;
     }
-    if (dec) {
-        // one cos / sin table per (Sp, theta): ModernBERT's global and local layers use two bases
-        const float thetas[2] = {c.rope_theta, c.backbone == GLC_BACKBONE_MODERNBERT ? c.rope_theta_local : c.rope_theta};
-        for (float theta : thetas) {
-            if (e->ropes.count({Sp, theta})) continue;
-            // Q2:86 inv_freq = 1 / base^(arange(0,d,2)/d) in float32; Q2:97-100 freqs = inv_freq * position, then cos / sin
-            const int hd2 = c.head_dim / 2;
-            std::vector<float> t((size_t)Sp * hd2 * 2);
-            for (int s = 0; s < Sp; ++s)
-                for (int i = 0; i < hd2; ++i) {
-                    const float inv = 1.0f / powf(theta, (float)(2 * i) / (float)c.head_dim);
-                    const float f = inv * (float)s;
-                    t[((size_t)s * hd2 + i) * 2] = cosf(f);
-                    t[((size_t)s * hd2 + i) * 2 + 1] = sinf(f);
-                }
-            float* d = (float*)dmalloc(e, t.size() * sizeof(float), false);
-            if (!d) return false;
-            if (hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_err("rope table upload failed"); return false; }
-            e->ropes[{Sp, theta}] = d;
-        }
-        return true;
-    }
+    if (dec) return build_rope_tables(e, Sp);
     const int rsel = round_up(B * (1 + (C > 0 ? C : 0)), 256);
     if (rsel > e->capSel) {
-        void** bufs[] = {&e->Xs, &e->Qs, &e->CTXs, &e->T1s, &e->H1s};
-        for (void** b : bufs) { dfree(e, *b); *b = dmalloc(e, (size_t)rsel * c.hidden * es); if (!*b) return false; }
-        dfree(e, e->FFs); e->FFs = dmalloc(e, (size_t)rsel * c.inter * es); if (!e->FFs) return false;
-        dfree(e, e->sel_b); dfree(e, e->sel_q);
-        e->sel_b = (int*)dmalloc(e, (size_t)rsel * sizeof(int)); e->sel_q = (int*)dmalloc(e, (size_t)rsel * sizeof(int));
-        if (!e->sel_b || !e->sel_q) return false;
+        for (void** b : {&e->Xs, &e->Qs, &e->CTXs, &e->T1s, &e->H1s}) if (!regrow(e, *b, (size_t)rsel * c.hidden * es)) return false;
+        if (!regrow(e, e->FFs, (size_t)rsel * c.inter * es) || !regrow(e, e->sel_b, (size_t)rsel * sizeof(int)) || !regrow(e, e->sel_q, (size_t)rsel * sizeof(int))) return false;
         e->capSel = rsel;
     }
-    {
-        const size_t nf = (size_t)round_up(B * Sp, 256) >> 5;      // one byte per 32-row tile of the padded row grid (the QKV GEMM reads 8 per 256-row tile)
-        if (nf > e->capFlag) { dfree(e, e->tile_flag); e->tile_flag = (unsigned char*)dmalloc(e, nf); if (!e->tile_flag) return false; e->capFlag = nf; }
+    const size_t nf = (size_t)Mpad >> 5;      // one byte per 32-row tile of the padded row grid (the QKV GEMM reads 8 per 256-row tile)
+    if (nf > e->capFlag) {
+        if (!regrow(e, e->tile_flag, nf)) return false;
+        e->capFlag = nf;
     }
-    if (!e->dtabs.count(Sp)) {
-        std::vector<int32_t> t(2 * Sp - 1);
-        glc_delta_table(Sp, c.pos_buckets, c.max_rel_pos, t.data());
-        int32_t* d = (int32_t*)dmalloc(e, t.size() * sizeof(int32_t), false);
-        if (!d) return false;
-        if (hipMemcpy(d, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { set_err("dtab upload failed"); return false; }
-        e->dtabs[Sp] = d;
-        {
-            // band-kernel addressing table: entry j <-> relative distance clamp(j - 64, 0, 2Sp-2) - (Sp-1); x = byte offset of PQ row
-            // delta in the Q fragment layout, y = byte offset of PK row delta in the K layout (pi on the row) — glc_layout.h
-            std::vector<int2> o(t.size() + 128);
-            for (size_t j = 0; j < o.size(); ++j) {
-                const long long r = (long long)j - 64;
-                const int dl = t[r < 0 ? 0 : (r > (long long)t.size() - 1 ? t.size() - 1 : (size_t)r)];
-                o[j].x = ((dl >> 5) * 2048 + (dl & 31) * 8) * (int)es;
-                o[j].y = ((dl >> 5) * 2048 + glc_pi32(dl & 31) * 8) * (int)es;
-            }
-            int2* od = (int2*)dmalloc(e, o.size() * sizeof(int2), false);
-            if (!od) return false;
-            if (hipMemcpy(od, o.data(), o.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) { set_err("otab upload failed"); return false; }
-            e->otabs[Sp] = od;
-            if (es == 4) {
-                // MX band kernel (attention_mx.hip, round 6): the same rows as ready-made load offsets into the PLANAR tile images of the position tables
-                // (glc_layout.h) — per lane half hh and entry j (NE = 2 Sp + 512 entries: 64 clamped ones in front, the rest behind, so that no index the
-                // kernel forms needs a clamp): .x = offset of the PQ row of entry j, .y = offset of the PK row of entry NE - 1 - j (the PK half runs
-                // BACKWARDS: a lane that adds its column c to a wave-uniform base walks the PQ rows up and the PK rows down with the same per-lane
-                // register); offset = tile * 8192 + slot * 16 + hh * 512: the lane's 16 bytes of f16 unit 0; unit s at + s * 1024, MX plane k at + 4096 + k * 1024
-                const int NE = 2 * Sp + 512;
-                std::vector<int2> m((size_t)2 * NE);
-                auto dl_of = [&](int j) { const long long r = (long long)j - 64; return t[r < 0 ? 0 : (r > (long long)t.size() - 1 ? t.size() - 1 : (size_t)r)]; };
-                for (int hh = 0; hh < 2; ++hh)
-                    for (int j = 0; j < NE; ++j) {
-                        const int dq = dl_of(j), dk = dl_of(NE - 1 - j);
-                        m[(size_t)hh * NE + j] = make_int2((dq >> 5) * 8192 + (dq & 31) * 16 + hh * 512, (dk >> 5) * 8192 + glc_pi32(dk & 31) * 16 + hh * 512);
-                    }
-                int2* md = (int2*)dmalloc(e, m.size() * sizeof(int2), false);
-                if (!md) return false;
-                if (hipMemcpy(md, m.data(), m.size() * sizeof(int2), hipMemcpyHostToDevice) != hipSuccess) { set_err("mtab upload failed"); return false; }
-                e->mtabs[Sp] = md;
-            }
-        }
-        // saturation points of the table: delta == P-1 for every q-k >= rsat_pos, delta == 0 for every q-k <= rsat_neg
-        int rp = Sp, rn = -Sp;
-        for (int r = Sp - 1; r >= -(Sp - 1) && t[r + Sp - 1] == 2 * (c.pos_buckets > 0 ? c.pos_buckets : c.max_rel_pos) - 1; --r) rp = r;
-        for (int r = -(Sp - 1); r <= Sp - 1 && t[r + Sp - 1] == 0; ++r) rn = r;
-        e->dsat[Sp] = std::make_pair(rp, rn);
-        // tables of the bucket-space MX attention (attention_mx2.hip); a table without the structure it needs keeps the band kernel
-        std::vector<unsigned char> idx16;
-        std::vector<int4> tinfo;
-        void* d_idx = nullptr; int4* d_ti = nullptr;
-        if (e->dtype == GLC_F32 && glc_mx2_build_tables(Sp, e->P, t.data(), idx16, tinfo)) {
-            d_idx = dmalloc(e, idx16.size(), false);
-            d_ti = (int4*)dmalloc(e, tinfo.size() * sizeof(int4), false);
-            if (!d_idx || !d_ti) return false;
-            if (hipMemcpy(d_idx, idx16.data(), idx16.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_ti, tinfo.data(), tinfo.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) { set_err("mx2 table upload failed"); return false; }
-        }
-        e->mx2tabs[Sp] = std::make_pair(d_idx, d_ti);
-    }
-    return true;
+    return build_position_tables(e, Sp);
 }
 
 // the scorer's tensors (after the 8 projector tensors): matrices that a GEMM reads are pre-split like the projectors', the last Linear
@@ -570,6 +559,91 @@ bool run_head_tail(glc_engine* e, int B, int C, float* d_logits) {
     return true;
 }
 
+inline int class_cap(const glc_engine* e) { return e->capC > 0 ? e->capC : 1; }
+
+// The start of every forward: profiler reset, the hidden-state dump buffer (keep_hidden: L + 1 slots of M rows), scan_rows.
+bool forward_prologue(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S) {
+    const glc_model_config& c = e->cfg;
+    if (e->profile) e->ev_used = 0;
+    if (e->keep_hidden) {
+        const size_t need = (size_t)(c.layers + 1) * B * round_up(S, 64) * c.hidden * esize(e->dtype);
+        if (need > e->hidden_cap) { dfree(e, e->hidden_dump); e->hidden_dump = dmalloc(e, need); if (!e->hidden_dump) return false; e->hidden_cap = need; }
+    }
+    Prof p(e, PC_SCAN);
+    KCHK(glc_launch_scan_rows(e->stream, ids, mask, B, S, c.class_token_index, c.embed_class_token, e->klen, e->kfirst, e->cls_pos, e->cls_cnt, class_cap(e)), false);
+    return true;
+}
+
+// keep_hidden: the M rows at src into slot `slot` of the dump buffer (0: embedding output, l + 1: output of layer l, L: the final rows)
+bool dump_hidden(glc_engine* e, int slot, const void* src, int M) {
+    if (!e->keep_hidden) return true;
+    const size_t n = (size_t)M * e->cfg.hidden * esize(e->dtype);
+    HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + slot * n, src, n, hipMemcpyDeviceToDevice, e->stream), false);
+    return true;
+}
+
+// The end of every forward: the head reads `rows` — the final rows of the backbone (gather + pooling), or the compact rows of
+// DeBERTa's pruned last layer (one [CLS] row and C class-token rows per text) — then the projectors and the scorer.
+bool forward_epilogue(glc_engine* e, const void* rows, bool compact, int B, int S, int C, float* d_logits) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, Sp = round_up(S, 64), dt = e->dtype;
+    hipStream_t st = e->stream;
+    if (C > 0) {
+        Prof p(e, PC_HEAD);
+        float* Gc = e->Gt + (size_t)round_up(B, 128) * H;
+        if (compact) KCHK(glc_launch_head_gather_sel(st, dt, rows, e->cls_pos, class_cap(e), e->Gt, Gc, B, H, C), false);
+        else {
+            KCHK(glc_launch_head_gather(st, dt, rows, e->cls_pos, class_cap(e), e->Gt, Gc, B, Sp, H, C, c.pooling == GLC_POOL_LAST ? e->klen : nullptr), false);
+            if (c.pooling == GLC_POOL_AVG) KCHK(glc_launch_pool_avg(st, dt, rows, e->kbias, e->Gt, B, Sp, H), false);
+        }
+        if (!run_head_tail(e, B, C, d_logits)) return false;
+    }
+    HIPCHK(hipGetLastError(), false);
+    e->lastB = B; e->lastS = S; e->lastSp = Sp;
+    return true;
+}
+
+// The group-split projections of a forward: the 256-tile split-f16 kernel (gemm256s.hip), or on the MX pipeline the cross-term kernel on GX rows
+struct GemmGs {
+    hipStream_t st; bool mx; int M;
+    const char* operator()(int epi, const GemmArgs& a) const {
+        if (!mx) return glc_launch_gemm256s_gs(st, epi, a);
+        GemmArgs gx = a; gx.gx_rows = M;          // fp8 range guard: the M rows of this forward, not the slack rows up to Mpad
+        return glc_launch_gemm256x(st, epi, gx);
+    }
+};
+
+// The gated FFN's first projection and its gate: FF = act(first) * second (decoder: silu(gate) * up, ModernBERT: gelu(input) * gate).
+// f1 = the [first | second] projection without its output (A, W, Mpad, N = 2I, K, the RMSNorm fold's operands); with the weight rows
+// interleaved (fused_swiglu) the gate runs in the GEMM epilogue, else as a pass of its own over the GU rows.
+struct Glu {
+    int epi;                                                                          // EPI_SWIGLU / EPI_GEGLU
+    const char* (*rows)(hipStream_t, int, const void*, void*, size_t, int, int);      // the gate over GU rows of T (last argument: interleaved columns)
+    const char* (*rows_gs)(hipStream_t, const float*, void*, size_t, int);            // ... over plain fp32 GU rows, group-split output
+};
+const Glu kSwiGlu{EPI_SWIGLU, glc_launch_swiglu, glc_launch_swiglu_gs}, kGeGlu{EPI_GEGLU, glc_launch_geglu, glc_launch_geglu_gs};
+
+bool gated_ffn(glc_engine* e, const Glu& glu, GemmArgs f1, bool gs, const GemmGs& gemm_gs, int M) {
+    hipStream_t st = e->stream;
+    const int dt = e->dtype, I = e->cfg.inter;
+    const bool fused = e->fused_swiglu;
+    // [first | second] rows: written only by the launches without the gate epilogue, allocated by the first forward that takes one
+    if (!(fused && (gs || dt != GLC_F32)) && e->capGU < f1.Mpad) {
+        dfree(e, e->GU); e->GU = dmalloc(e, (size_t)f1.Mpad * 2 * I * esize(dt));
+        if (!e->GU) return false;
+        e->capGU = f1.Mpad;
+    }
+    f1.C = e->GU;
+    Prof p(e, PC_FFN1);
+    if (fused && gs) { f1.C = e->FF; KCHK(gemm_gs(glu.epi, f1), false); }
+    else if (fused && dt == GLC_F32) {      // small forward of the fp32 mode: plain rows, interleaved columns
+        KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glu.rows(st, dt, e->GU, e->FF, (size_t)M, I, 1), false); }
+    else if (fused) { f1.C = e->FF; KCHK(glc_launch_gemm256s(st, dt, glu.epi, f1), false); }
+    else if (gs) { f1.gs_c_plain = 1; KCHK(gemm_gs(EPI_BIAS, f1), false); KCHK(glu.rows_gs(st, (const float*)e->GU, e->FF, (size_t)M, I), false); }
+    else { KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glu.rows(st, dt, e->GU, e->FF, (size_t)M, I, 0), false); }
+    return true;
+}
+
 // Decoder-style backbone: one launch sequence per batch (Q2:384-398).  Pre-norm residual stream X (operand type T).
 bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
     const glc_model_config& c = e->cfg;
@@ -579,21 +653,14 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
     hipStream_t st = e->stream;
     const int dt = e->dtype;
     const size_t es = esize(dt);
-    const int ccap = e->capC > 0 ? e->capC : 1;
-    if (e->profile) { e->ev_used = 0; }
     GxScope gx_scope(e);                     // fp8 range guard + activation exponent: the launchers of this thread hand them to every producer / reader of GX rows and MX tiles
-    if (e->keep_hidden) {
-        const size_t need = (size_t)(L + 1) * M * H * es;
-        if (need > e->hidden_cap) { dfree(e, e->hidden_dump); e->hidden_dump = dmalloc(e, need); if (!e->hidden_dump) return false; e->hidden_cap = need; }
-    }
-    { Prof p(e, PC_SCAN);
-      KCHK(glc_launch_scan_rows(st, ids, mask, B, S, c.class_token_index, c.embed_class_token, e->klen, e->kfirst, e->cls_pos, e->cls_cnt, ccap), false); }
+    if (!forward_prologue(e, ids, mask, B, S)) return false;
     { Prof p(e, PC_EMBED);
       KCHK(glc_launch_embed_plain(st, dt, ids, mask, e->emb, e->X, e->kbias, B, S, Sp, H, c.vocab, c.pad_id), false); }
-    if (e->keep_hidden) HIPCHK(hipMemcpyAsync(e->hidden_dump, e->X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+    if (!dump_hidden(e, 0, e->X, M)) return false;
     const float qscale = 1.4426950408889634f / sqrtf((float)d);         // Q2:186 scaling, times log2(e) for the exp2 softmax
     const bool mfma = (dt != GLC_F32 || e->dec_split) && e->attn_impl != 1;   // flash-style MFMA kernel (fp32 mode: on split-f16 units); impl 1 / native fp32: straightforward kernel
-    // group-split pipeline of the fp32 mode (see run_forward): the GEMM A operands (RMSNorm outputs, context rows, SwiGLU output) are
+    // group-split pipeline of the fp32 mode (see run_forward_deberta): the GEMM A operands (RMSNorm outputs, context rows, SwiGLU output) are
     // written as [32 hi | 32 lo] groups by their producers and every projection runs on the 256-tile LDS-DMA kernel; the residual
     // stream X, the fused QKV rows (RoPE / layout pass) and the [gate | up] rows stay plain fp32
     bool gs = false;
@@ -617,11 +684,7 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
     e->last_mx = mx;
     const bool mxa = mx && mfma && e->mx_attn;      // round 4: the attention of the MX pipeline on MX tiles too (decoder_mx.hip)
     e->last_mx_attn = mxa;
-    auto gemm_gs = [&](int epi, const GemmArgs& ga) -> const char* {
-        if (!mx) return glc_launch_gemm256s_gs(st, epi, ga);
-        GemmArgs gx = ga; gx.gx_rows = M;          // fp8 range guard: the M rows of this forward, not the slack rows up to Mpad
-        return glc_launch_gemm256x(st, epi, gx);
-    };
+    const GemmGs gemm_gs{st, mx, M};
     if (rnf) {      // the embedding rows enter the pipeline: plain fp32 (X2) -> raw group-split rows (X) + statistics
         HIPCHK(hipMemcpyAsync(e->X2, e->X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
         KCHK(glc_launch_rows_to_gs_rms(st, (const float*)e->X2, e->X, sX, c.ln_eps, M, H, mx ? 1 : 0), false);
@@ -658,23 +721,11 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
         { Prof p(e, PC_LN); KCHK(rnf ? glc_launch_ln_stats(st, e->ln_part, H / 64, sX, M, H, c.ln_eps, 1)
                                  : gs ? glc_launch_rmsnorm_gs(st, (const float*)X, e->H1, w.ln2, c.ln_eps, M, H)
                                       : glc_launch_rmsnorm(st, dt, X, e->H1, w.ln2, c.ln_eps, M, H), false); }                        // Q2:295
-        const bool need_gu = !(e->fused_swiglu && (gs || dt != GLC_F32));
-        if (need_gu && e->capGU < Mpad) {
-            dfree(e, e->GU); e->GU = dmalloc(e, (size_t)Mpad * 2 * I * es);
-            if (!e->GU) return false;
-            e->capGU = Mpad;
-        }
         GemmArgs f1;
-        f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.C = e->GU; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
+        f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
         if (rnf) { f1.A = X; f1.W = w.Wguf; f1.a_stats = sX; }
         if (mx) { f1.W = w.Wguf_x; f1.mx_ws = w.ws_guf; }
-        { Prof p(e, PC_FFN1);                                                                                                  // Q2:47 silu(gate) * up
-          if (e->fused_swiglu && gs) { f1.C = e->FF; KCHK(gemm_gs(EPI_SWIGLU, f1), false); }
-          else if (e->fused_swiglu && dt == GLC_F32) {      // small forward of the fp32 mode: plain rows, interleaved [gate | up] columns
-              KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glc_launch_swiglu(st, dt, e->GU, e->FF, (size_t)M, I, 1), false); }
-          else if (e->fused_swiglu) { f1.C = e->FF; KCHK(glc_launch_gemm256s(st, dt, EPI_SWIGLU, f1), false); }
-          else if (gs) { f1.gs_c_plain = 1; KCHK(glc_launch_gemm256s_gs(st, EPI_BIAS, f1), false); KCHK(glc_launch_swiglu_gs(st, (const float*)e->GU, e->FF, (size_t)M, I), false); }
-          else { KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glc_launch_swiglu(st, dt, e->GU, e->FF, (size_t)M, I), false); } }
+        if (!gated_ffn(e, kSwiGlu, f1, gs, gemm_gs, M)) return false;                                                          // Q2:47 silu(gate) * up
         GemmArgs f2;
         f2.A = e->FF; f2.W = w.Wd; f2.bias = nullptr; f2.C = Xn; f2.resid = X; f2.Mpad = Mpad; f2.N = H; f2.K = I; f2.gs_resid_plain = 1;
         if (rnf) { f2.gs_resid_plain = 0; if (l + 1 < L) f2.ln_part = e->ln_part; }      // (the last layer hands plain fp32 rows to the final norm)
@@ -682,21 +733,11 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
         { Prof p(e, PC_FFN2); KCHK(gs ? gemm_gs(EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }
         std::swap(X, Xn); std::swap(sX, sXn);
         if (rnf && l + 1 < L) { Prof p(e, PC_LN); KCHK(glc_launch_ln_stats(st, e->ln_part, H / 64, sX, M, H, c.ln_eps, 1), false); }
-        if (e->keep_hidden && l + 1 < L)
-            HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)(l + 1) * M * H * es, X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+        if (l + 1 < L && !dump_hidden(e, l + 1, X, M)) return false;
     }
     { Prof p(e, PC_LN); KCHK(glc_launch_rmsnorm(st, dt, X, e->H1, e->final_norm, c.ln_eps, M, H), false); }                    // Q2:398
-    if (e->keep_hidden) HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)L * M * H * es, e->H1, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
-    if (C > 0) {
-        Prof p(e, PC_HEAD);
-        float* Gc = e->Gt + (size_t)round_up(B, 128) * H;
-        KCHK(glc_launch_head_gather(st, dt, e->H1, e->cls_pos, ccap, e->Gt, Gc, B, Sp, H, C, c.pooling == GLC_POOL_LAST ? e->klen : nullptr), false);
-        if (c.pooling == GLC_POOL_AVG) KCHK(glc_launch_pool_avg(st, dt, e->H1, e->kbias, e->Gt, B, Sp, H), false);
-        if (!run_head_tail(e, B, C, d_logits)) return false;
-    }
-    HIPCHK(hipGetLastError(), false);
-    e->lastB = B; e->lastS = S; e->lastSp = Sp;
-    return true;
+    if (!dump_hidden(e, L, e->H1, M)) return false;
+    return forward_epilogue(e, e->H1, false, B, S, C, d_logits);
 }
 
 // ModernBERT backbone (transformers models/modernbert/modeling_modernbert.py, cited as MB:<line>): one launch sequence per batch.
@@ -709,20 +750,12 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     hipStream_t st = e->stream;
     const int dt = e->dtype;
-    const size_t es = esize(dt);
-    const int ccap = e->capC > 0 ? e->capC : 1;
-    if (e->profile) { e->ev_used = 0; }
-    if (e->keep_hidden) {
-        const size_t need = (size_t)(L + 1) * M * H * es;
-        if (need > e->hidden_cap) { dfree(e, e->hidden_dump); e->hidden_dump = dmalloc(e, need); if (!e->hidden_dump) return false; e->hidden_cap = need; }
-    }
-    { Prof p(e, PC_SCAN);
-      KCHK(glc_launch_scan_rows(st, ids, mask, B, S, c.class_token_index, c.embed_class_token, e->klen, e->kfirst, e->cls_pos, e->cls_cnt, ccap), false); }
+    if (!forward_prologue(e, ids, mask, B, S)) return false;
     void *X = e->X, *Xn = e->X2;
     { Prof p(e, PC_EMBED);                                                                                                   // MB:52-71
       KCHK(glc_launch_embed_plain(st, dt, ids, mask, e->emb, Xn, e->kbias, B, S, Sp, H, c.vocab, c.pad_id), false);
       KCHK(glc_launch_layernorm(st, dt, Xn, X, e->eln_g, e->zero_bias, c.ln_eps, M, H), false); }
-    if (e->keep_hidden) HIPCHK(hipMemcpyAsync(e->hidden_dump, X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+    if (!dump_hidden(e, 0, X, M)) return false;
     const float qscale = 1.4426950408889634f / sqrtf((float)d);         // head_dim^-1/2, times log2(e) for the exp2 softmax
     const bool mfma = (dt != GLC_F32 || e->dec_split) && e->attn_impl != 1;
     // group-split pipeline of the fp32 mode (as the decoder's, without the norm fold): LayerNorm / context / GeGLU rows are written as
@@ -735,6 +768,7 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
     }
     e->last_gs = gs;
     e->last_lnf = false; e->last_mx = false; e->last_mx_attn = false;
+    const GemmGs gemm_gs{st, false, M};
     auto norm = [&](const void* src, const float* gamma) -> const char* {      // H1 = LN(src) (group-split rows in the gs pipeline)
         return gs ? glc_launch_layernorm_gs(st, (const float*)src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H)
                   : glc_launch_layernorm(st, dt, src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H);
@@ -751,7 +785,7 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
         GemmArgs g;
         g.A = (l == 0 && !gs) ? X : e->H1; g.W = w.Wqkv; g.bias = nullptr; g.C = e->QKV; g.Mpad = Mpad; g.N = 3 * H; g.K = H; g.gs_c_plain = 1;
         { Prof p(e, PC_QKV);
-          KCHK(gs ? glc_launch_gemm256s_gs(st, EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                  // MB:274-279
+          KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                                      // MB:274-279
           if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);   // MB:281-282 RoPE
           else KCHK(glc_launch_rope_qk(st, dt, e->QKV, cs, M, Sp, nh, nh, d, qscale), false); }
         { Prof p(e, PC_ATTN);                                                                                                // MB:284-297
@@ -759,65 +793,33 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
           else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nh, nh, d, 0, win), false); }
         GemmArgs o;
         o.A = e->CTX; o.W = w.Wo; o.bias = nullptr; o.C = Xn; o.resid = X; o.Mpad = Mpad; o.N = H; o.K = H; o.gs_resid_plain = 1;
-        { Prof p(e, PC_ATTN_OUT); KCHK(gs ? glc_launch_gemm256s_gs(st, EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }   // MB:299, :332
+        { Prof p(e, PC_ATTN_OUT); KCHK(gs ? gemm_gs(EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }   // MB:299, :332
         std::swap(X, Xn);
         { Prof p(e, PC_LN); KCHK(norm(X, w.ln2), false); }                                                                  // MB:333
-        const bool need_gu = !(e->fused_swiglu && (gs || dt != GLC_F32));
-        if (need_gu && e->capGU < Mpad) {
-            dfree(e, e->GU); e->GU = dmalloc(e, (size_t)Mpad * 2 * I * es);
-            if (!e->GU) return false;
-            e->capGU = Mpad;
-        }
         GemmArgs f1;
-        f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.C = e->GU; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
-        { Prof p(e, PC_FFN1);                                                                                                // MB:89-91 gelu(input) * gate
-          if (e->fused_swiglu && gs) { f1.C = e->FF; KCHK(glc_launch_gemm256s_gs(st, EPI_GEGLU, f1), false); }
-          else if (e->fused_swiglu && dt == GLC_F32) {      // small forward of the fp32 mode: plain rows, interleaved [input | gate] columns
-              KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glc_launch_geglu(st, dt, e->GU, e->FF, (size_t)M, I, 1), false); }
-          else if (e->fused_swiglu) { f1.C = e->FF; KCHK(glc_launch_gemm256s(st, dt, EPI_GEGLU, f1), false); }
-          else if (gs) { f1.gs_c_plain = 1; KCHK(glc_launch_gemm256s_gs(st, EPI_BIAS, f1), false); KCHK(glc_launch_geglu_gs(st, (const float*)e->GU, e->FF, (size_t)M, I), false); }
-          else { KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false); KCHK(glc_launch_geglu(st, dt, e->GU, e->FF, (size_t)M, I), false); } }
+        f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
+        if (!gated_ffn(e, kGeGlu, f1, gs, gemm_gs, M)) return false;                                                        // MB:89-91 gelu(input) * gate
         GemmArgs f2;
         f2.A = e->FF; f2.W = w.Wd; f2.bias = nullptr; f2.C = Xn; f2.resid = X; f2.Mpad = Mpad; f2.N = H; f2.K = I; f2.gs_resid_plain = 1;
-        { Prof p(e, PC_FFN2); KCHK(gs ? glc_launch_gemm256s_gs(st, EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }
+        { Prof p(e, PC_FFN2); KCHK(gs ? gemm_gs(EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }
         std::swap(X, Xn);
-        if (e->keep_hidden && l + 1 < L)
-            HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)(l + 1) * M * H * es, X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+        if (l + 1 < L && !dump_hidden(e, l + 1, X, M)) return false;
     }
     { Prof p(e, PC_LN); KCHK(glc_launch_layernorm(st, dt, X, e->H1, e->final_norm, e->zero_bias, c.ln_eps, M, H), false); }   // MB:476
-    if (e->keep_hidden) HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)L * M * H * es, e->H1, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
-    if (C > 0) {
-        Prof p(e, PC_HEAD);
-        float* Gc = e->Gt + (size_t)round_up(B, 128) * H;
-        KCHK(glc_launch_head_gather(st, dt, e->H1, e->cls_pos, ccap, e->Gt, Gc, B, Sp, H, C, c.pooling == GLC_POOL_LAST ? e->klen : nullptr), false);
-        if (c.pooling == GLC_POOL_AVG) KCHK(glc_launch_pool_avg(st, dt, e->H1, e->kbias, e->Gt, B, Sp, H), false);
-        if (!run_head_tail(e, B, C, d_logits)) return false;
-    }
-    HIPCHK(hipGetLastError(), false);
-    e->lastB = B; e->lastS = S; e->lastSp = Sp;
-    return true;
+    if (!dump_hidden(e, L, e->H1, M)) return false;
+    return forward_epilogue(e, e->H1, false, B, S, C, d_logits);
 }
 
-// The launch sequence for one batch.  ids/mask are device pointers.
-bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
-    if (e->cfg.backbone == GLC_BACKBONE_DECODER) return run_forward_decoder(e, ids, mask, B, S, C, d_logits);
-    if (e->cfg.backbone == GLC_BACKBONE_MODERNBERT) return run_forward_modernbert(e, ids, mask, B, S, C, d_logits);
+// DeBERTa-v3 backbone: one launch sequence per batch (post-norm encoder with disentangled relative-position attention).
+bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, I = c.inter, nh = c.heads;
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     hipStream_t st = e->stream;
     const int dt = e->dtype;
-    const size_t es = esize(dt);
-    const int ccap = e->capC > 0 ? e->capC : 1;
-    if (e->profile) { e->ev_used = 0; }
+    const int ccap = class_cap(e);
     GxScope gx_scope(e);                     // fp8 range guard + activation exponent (see run_forward_decoder)
-
-    if (e->keep_hidden) {
-        const size_t need = (size_t)(c.layers + 1) * M * H * es;
-        if (need > e->hidden_cap) { dfree(e, e->hidden_dump); e->hidden_dump = dmalloc(e, need); if (!e->hidden_dump) return false; e->hidden_cap = need; }
-    }
-    { Prof p(e, PC_SCAN);
-      KCHK(glc_launch_scan_rows(st, ids, mask, B, S, c.class_token_index, c.embed_class_token, e->klen, e->kfirst, e->cls_pos, e->cls_cnt, ccap), false); }
+    if (!forward_prologue(e, ids, mask, B, S)) return false;
     // attention kernel: 3 = workgroup-shared band kernel (attention_wg.hip), 2 = per-wave band kernel (every operand type; fp32 native:
     // 32x32x2 MFMAs), 1 = straightforward kernel.  Default, measured same-box at c3 (scripts/attn_bench.py): split-f16 units of the
     // fp32 mode -> 3 (1.45 vs 1.80 ms per launch: MFMA-heavy, the 3 shared p2c MFMA blocks and the shared K / V^T ring pay);
@@ -850,11 +852,7 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
     for (int l = 0; mx && l < c.layers; ++l) mx = e->layers[l].W1f_x && e->layers[l].Wqkv_x && e->layers[l].Wo_x && e->layers[l].W2_x && (l == 0 || e->layers[l].Wqkvf_x);
     e->last_mx = mx;
     e->last_mx_attn = false;
-    auto gemm_gs = [&](int epi, const GemmArgs& ga) -> const char* {
-        if (!mx) return glc_launch_gemm256s_gs(st, epi, ga);
-        GemmArgs gx = ga; gx.gx_rows = M;          // fp8 range guard: the M rows of this forward, not the slack rows up to Mpad
-        return glc_launch_gemm256x(st, epi, gx);
-    };
+    const GemmGs gemm_gs{st, mx, M};
     // 16-bit modes: the same LayerNorm fold on plain rows of T, when all four projections of a layer run on the staggered 256-tile kernel
     bool fold16 = false;
     if (dt != GLC_F32 && e->ln_fused && prune && !e->keep_hidden && e->attn_impl != 1 && H % 256 == 0 && I % 256 == 0 && e->statsA && e->statsB && e->ln_part) {
@@ -864,7 +862,7 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
     { Prof p(e, PC_EMBED);
       if (gs) KCHK(glc_launch_embed_gs(st, ids, mask, (const float*)e->emb, e->eln_g, e->eln_b, c.ln_eps, e->X, e->kbias, B, S, Sp, H, c.vocab, c.pad_id, mx ? 1 : 0), false);
       else KCHK(glc_launch_embed(st, dt, ids, mask, e->emb, e->eln_g, e->eln_b, c.ln_eps, e->X, e->kbias, B, S, Sp, H, c.vocab, c.pad_id), false); }
-    if (e->keep_hidden) HIPCHK(hipMemcpyAsync(e->hidden_dump, e->X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+    if (!dump_hidden(e, 0, e->X, M)) return false;
 
     bool x_is_raw = false;
     for (int l = 0; l < c.layers; ++l) {
@@ -929,8 +927,7 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
                                       : glc_launch_layernorm(st, dt, e->T1, e->X, w.ln2g, w.ln2b, c.ln_eps, M, H), false); }
         x_is_raw = next_raw;
         if (e->debug_stop == 10 * l + 4) return true;
-        if (e->keep_hidden)
-            HIPCHK(hipMemcpyAsync((char*)e->hidden_dump + (size_t)(l + 1) * M * H * es, e->X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
+        if (!dump_hidden(e, l + 1, e->X, M)) return false;
     }
     const int Cc = C > 0 ? C : 0;
     if (prune) {
@@ -981,197 +978,134 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
         KCHK(launch_gemm_auto(e, dt, EPI_RESID, f2), false);
         KCHK(glc_launch_layernorm(st, dt, e->T1s, e->Xs, w.ln2g, w.ln2b, c.ln_eps, R, H), false);
     }
-    if (C > 0) {
-        Prof p(e, PC_HEAD);
-        float* Gc = e->Gt + (size_t)round_up(B, 128) * H;
-        if (prune) KCHK(glc_launch_head_gather_sel(st, dt, e->Xs, e->cls_pos, ccap, e->Gt, Gc, B, H, C), false);
-        else {
-            KCHK(glc_launch_head_gather(st, dt, e->X, e->cls_pos, ccap, e->Gt, Gc, B, Sp, H, C, c.pooling == GLC_POOL_LAST ? e->klen : nullptr), false);
-            if (c.pooling == GLC_POOL_AVG) KCHK(glc_launch_pool_avg(st, dt, e->X, e->kbias, e->Gt, B, Sp, H), false);
-        }
-        if (!run_head_tail(e, B, C, d_logits)) return false;
+    return forward_epilogue(e, prune ? e->Xs : e->X, prune, B, S, C, d_logits);
+}
+
+// The launch sequence for one batch.  ids/mask are device pointers.
+bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
+    switch (e->cfg.backbone) {
+    case GLC_BACKBONE_DECODER: return run_forward_decoder(e, ids, mask, B, S, C, d_logits);
+    case GLC_BACKBONE_MODERNBERT: return run_forward_modernbert(e, ids, mask, B, S, C, d_logits);
+    default: return run_forward_deberta(e, ids, mask, B, S, C, d_logits);
     }
-    HIPCHK(hipGetLastError(), false);
-    e->lastB = B; e->lastS = S; e->lastSp = Sp;
+}
+
+// the largest tensor (in floats) a backbone's loader sends through the staging buffer: the embedding, the fused QKV weight (the folded
+// copy goes up in one piece) or the FFN's input weight (the gated FFNs' [first | second] rows in one piece)
+size_t staging_floats(const glc_model_config& c) {
+    const size_t H = c.hidden, I = c.inter;
+    const size_t qkv = c.backbone == GLC_BACKBONE_DECODER ? (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim : 3 * H;
+    const size_t ffn = c.backbone == GLC_BACKBONE_DEBERTA ? I : 2 * I;
+    return std::max({(size_t)c.vocab * H, qkv * H, ffn * H});
+}
+
+// one projection weight: the slot of its device copy and its host row blocks, in order
+struct Proj { void** dst; std::vector<std::pair<const float*, size_t>> parts; };
+// A layer's projection weights: each allocated as T and uploaded from its row blocks, then (fp32 mode) split into group-split rows
+// once — the operand image of both split-f16 GEMM kernels
+bool upload_projections(glc_engine* e, float* staging, std::initializer_list<Proj> ws) {
+    const size_t es = esize(e->dtype);
+    for (const Proj& p : ws) {
+        size_t n = 0;
+        for (const auto& part : p.parts) n += part.second;
+        *p.dst = dmalloc(e, n * es, false);
+        if (!*p.dst) return false;
+        size_t off = 0;
+        for (const auto& part : p.parts) {
+            if (!upload_as(e, part.first, part.second, (char*)*p.dst + off * es, staging)) return false;
+            off += part.second;
+        }
+        if (e->w_presplit && e->dtype == GLC_F32) KCHK(glc_launch_presplit(e->stream, *p.dst, n), false);
+    }
+    return true;
+}
+
+// The weight rows of a gated FFN that runs its gate in the GEMM epilogue (fused_swiglu): rows [32 f, 32 f + 16) = the first half's rows of
+// features 16 f .. 16 f + 15 (decoder gate, ModernBERT input), rows [32 f + 16, 32 f + 32) = the second half's rows of the same features
+void interleave_glu_rows(const float* first, const float* second, int I, int H, std::vector<float>& dst) {
+    dst.resize(2 * (size_t)I * H);
+    for (int f = 0; f < I / 16; ++f) {
+        memcpy(dst.data() + (size_t)(32 * f) * H, first + (size_t)(16 * f) * H, (size_t)16 * H * sizeof(float));
+        memcpy(dst.data() + (size_t)(32 * f + 16) * H, second + (size_t)(16 * f) * H, (size_t)16 * H * sizeof(float));
+    }
+}
+
+// The head (the last tensors of every backbone): the two FeaturesProjectors' 8 tensors and the scorer's, then the load's final sync
+bool upload_head(glc_engine* e, const float* const* ht) {
+    const size_t H = e->cfg.hidden;
+    for (int i = 0; i < 8; ++i) {
+        e->headw[i] = upload_f32(e, ht[i], i % 2 == 0 ? H * H : H);
+        if (!e->headw[i]) return false;
+        if (i % 2 == 0 && e->w_presplit) KCHK(glc_launch_presplit(e->stream, e->headw[i], H * H), false);
+    }
+    if (!upload_scorer(e, ht + GLC_TENSORS_HEAD)) return false;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); return false; }
     return true;
 }
 
 // Decoder backbone: upload + convert weights.  Fused operands: Wqkv = [q_proj; k_proj; v_proj] rows, Wgu = [gate_proj; up_proj]
 // rows, so each layer runs four GEMMs (Q2:206-208 as one, Q2:233, Q2:47 gate|up as one, down).
-bool create_decoder(glc_engine* e, const float* const* tensors) {
+bool create_decoder(glc_engine* e, const float* const* tensors, float* staging) {
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, I = c.inter, L = c.layers, d = c.head_dim;
-    const size_t NQ = (size_t)c.heads * d, NKV = (size_t)c.kv_heads * d, NQKV = NQ + 2 * NKV;
-    const size_t es = esize(e->dtype);
-    if (NQ % 128 || NKV % 64 || NQKV % 128) { set_err("engine_create: decoder projection widths must be multiples of 128"); return false; }
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return false; }
-    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { set_err("event create failed"); return false; }
-    size_t stage_n = (size_t)c.vocab * H;
-    if ((size_t)I * H > stage_n) stage_n = (size_t)I * H;
-    if (NQ * H > stage_n) stage_n = NQ * H;
-    if (2 * (size_t)I * H > stage_n) stage_n = 2 * (size_t)I * H;
-    float* staging = nullptr;
-    if (hipMalloc((void**)&staging, stage_n * sizeof(float)) != hipSuccess) { set_err("staging alloc failed"); return false; }
-    bool ok = false;
-    do {
-        e->emb = dmalloc(e, (size_t)c.vocab * H * es, false);
-        if (!e->emb || !upload_as(e, tensors[0], (size_t)c.vocab * H, e->emb, staging)) break;
-        e->dlayers.resize(L);
-        // SwiGLU in the epilogue of the staggered 256-tile GEMM when the shapes allow it (16-bit operands)
-        // (fp32 mode: the group-split 256-tile GEMM has the same epilogue; its small-forward fallback un-fuses on the interleaved columns)
-        e->fused_swiglu = (e->dtype != GLC_F32 || (e->w_presplit && e->dec_split && H % 256 == 0)) && (2 * I) % 256 == 0 && H % 32 == 0 && I % 16 == 0 &&
-                          glc_dev_env("GLC_NO_FUSED_SWIGLU") == nullptr;
-        std::vector<float> bqkv(NQKV), gu_host(e->fused_swiglu ? 2 * (size_t)I * H : 0), fold_host;
-        bool lok = true;
-        for (int l = 0; l < L && lok; ++l) {
-            const float* const* t = tensors + 1 + GLC_DEC_TENSORS_PER_LAYER * l;    // ln1 qw qb kw kb vw vb ow ln2 gw uw dw
-            DecLayerW& w = e->dlayers[l];
-            w.Wqkv = dmalloc(e, NQKV * H * es, false);
-            w.Wo = dmalloc(e, (size_t)H * NQ * es, false);
-            w.Wgu = dmalloc(e, 2 * (size_t)I * H * es, false);
-            w.Wd = dmalloc(e, (size_t)H * I * es, false);
-            if (!w.Wqkv || !w.Wo || !w.Wgu || !w.Wd) { lok = false; break; }
-            lok = upload_as(e, t[1], NQ * H, w.Wqkv, staging) && upload_as(e, t[3], NKV * H, (char*)w.Wqkv + NQ * H * es, staging) &&
-                  upload_as(e, t[5], NKV * H, (char*)w.Wqkv + (NQ + NKV) * H * es, staging) && upload_as(e, t[7], (size_t)H * NQ, w.Wo, staging) &&
-                  upload_as(e, t[11], (size_t)H * I, w.Wd, staging);
-            if (lok && e->fused_swiglu) {
-                // rows [32 f, 32 f + 16) = gate rows of features 16 f .. 16 f + 15, rows [32 f + 16, 32 f + 32) = their up rows
-                for (int f = 0; f < I / 16; ++f) {
-                    memcpy(gu_host.data() + (size_t)(32 * f) * H, t[9] + (size_t)(16 * f) * H, (size_t)16 * H * sizeof(float));
-                    memcpy(gu_host.data() + (size_t)(32 * f + 16) * H, t[10] + (size_t)(16 * f) * H, (size_t)16 * H * sizeof(float));
-                }
-                lok = upload_as(e, gu_host.data(), 2 * (size_t)I * H, w.Wgu, staging);
-            } else if (lok) {
-                lok = upload_as(e, t[9], (size_t)I * H, w.Wgu, staging) && upload_as(e, t[10], (size_t)I * H, (char*)w.Wgu + (size_t)I * H * es, staging);
-            }
-            if (!lok) break;
-            if (e->w_presplit && e->dtype == GLC_F32) {     // group-split weight rows (the operand image of both split-f16 GEMM kernels)
-                const char* pm = glc_launch_presplit(e->stream, w.Wqkv, NQKV * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wo, (size_t)H * NQ);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wgu, 2 * (size_t)I * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wd, (size_t)H * I);
-                if (pm) { set_err(pm); lok = false; break; }
-            }
-            if (e->ln_fused && e->w_presplit && e->dtype == GLC_F32 && e->fused_swiglu && H % 64 == 0) {
-                // RMSNorm folded into the consumer GEMMs of the group-split pipeline: RMSNorm(x) W^T = rstd (x (W diag(gamma))^T)
-                auto fold_rows = [&](const float* Wsrc, size_t rows, const float* gam, float* dst) {
-                    for (size_t n = 0; n < rows; ++n) for (int k = 0; k < H; ++k) dst[n * H + k] = Wsrc[n * H + k] * gam[k];
-                };
-                std::vector<float>& wf = fold_host;
-                wf.resize(2 * (size_t)I * H > NQKV * H ? 2 * (size_t)I * H : NQKV * H);
-                fold_rows(t[1], NQ, t[0], wf.data()); fold_rows(t[3], NKV, t[0], wf.data() + NQ * H); fold_rows(t[5], NKV, t[0], wf.data() + (NQ + NKV) * H);
-                w.Wqkvf = dmalloc(e, NQKV * H * es, false);
-                if (!w.Wqkvf || !upload_as(e, wf.data(), NQKV * H, w.Wqkvf, staging)) { lok = false; break; }
-                const char* pm = glc_launch_presplit(e->stream, w.Wqkvf, NQKV * H);
-                if (pm) { set_err(pm); lok = false; break; }
-                fold_rows(gu_host.data(), 2 * (size_t)I, t[8], wf.data());           // the interleaved [16 gate | 16 up] row order is kept
-                w.Wguf = dmalloc(e, 2 * (size_t)I * H * es, false);
-                if (!w.Wguf || !upload_as(e, wf.data(), 2 * (size_t)I * H, w.Wguf, staging)) { lok = false; break; }
-                pm = glc_launch_presplit(e->stream, w.Wguf, 2 * (size_t)I * H);
-                if (pm) { set_err(pm); lok = false; break; }
-            }
-            for (size_t i = 0; i < NQ; ++i) bqkv[i] = t[2][i];
-            for (size_t i = 0; i < NKV; ++i) { bqkv[NQ + i] = t[4][i]; bqkv[NQ + NKV + i] = t[6][i]; }
-            w.bqkv = upload_f32(e, bqkv.data(), NQKV);
-            w.ln1 = upload_f32(e, t[0], H); w.ln2 = upload_f32(e, t[8], H);
-            if (!w.bqkv || !w.ln1 || !w.ln2) { lok = false; break; }
-            if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); lok = false; break; }   // bqkv host buffer is reused
+    const size_t NQ = (size_t)c.heads * d, NKV = (size_t)c.kv_heads * d, NQKV = NQ + 2 * NKV, IH = (size_t)I * H;
+    e->dlayers.resize(L);
+    std::vector<float> bqkv(NQKV), gu_host, fold_host;
+    for (int l = 0; l < L; ++l) {
+        const float* const* t = tensors + 1 + GLC_DEC_TENSORS_PER_LAYER * l;    // ln1 qw qb kw kb vw vb ow ln2 gw uw dw
+        DecLayerW& w = e->dlayers[l];
+        if (e->fused_swiglu) interleave_glu_rows(t[9], t[10], I, H, gu_host);
+        const Proj gu = e->fused_swiglu ? Proj{&w.Wgu, {{gu_host.data(), 2 * IH}}} : Proj{&w.Wgu, {{t[9], IH}, {t[10], IH}}};
+        if (!upload_projections(e, staging, {{&w.Wqkv, {{t[1], NQ * H}, {t[3], NKV * H}, {t[5], NKV * H}}}, {&w.Wo, {{t[7], H * NQ}}}, gu, {&w.Wd, {{t[11], IH}}}}))
+            return false;
+        if (e->ln_fused && e->w_presplit && e->dtype == GLC_F32 && e->fused_swiglu && H % 64 == 0) {
+            // RMSNorm folded into the consumer GEMMs of the group-split pipeline: RMSNorm(x) W^T = rstd (x (W diag(gamma))^T)
+            auto fold_rows = [&](const float* Wsrc, size_t rows, const float* gam, float* dst) {
+                for (size_t n = 0; n < rows; ++n) for (int k = 0; k < H; ++k) dst[n * H + k] = Wsrc[n * H + k] * gam[k];
+            };
+            std::vector<float>& wf = fold_host;
+            wf.resize(2 * IH > NQKV * H ? 2 * IH : NQKV * H);
+            fold_rows(t[1], NQ, t[0], wf.data()); fold_rows(t[3], NKV, t[0], wf.data() + NQ * H); fold_rows(t[5], NKV, t[0], wf.data() + (NQ + NKV) * H);
+            if (!upload_projections(e, staging, {{&w.Wqkvf, {{wf.data(), NQKV * H}}}})) return false;
+            fold_rows(gu_host.data(), 2 * (size_t)I, t[8], wf.data());           // the interleaved [16 gate | 16 up] row order is kept
+            if (!upload_projections(e, staging, {{&w.Wguf, {{wf.data(), 2 * IH}}}})) return false;
         }
-        if (!lok) break;
-        e->final_norm = upload_f32(e, tensors[1 + GLC_DEC_TENSORS_PER_LAYER * L], H);
-        if (!e->final_norm) break;
-        const float* const* ht = tensors + 2 + GLC_DEC_TENSORS_PER_LAYER * L;
-        bool hok = true;
-        for (int i = 0; i < 8 && hok; ++i) {
-            e->headw[i] = upload_f32(e, ht[i], (i % 2 == 0) ? (size_t)H * H : (size_t)H); hok = e->headw[i] != nullptr;
-            if (hok && (i % 2 == 0) && e->w_presplit) { const char* pm = glc_launch_presplit(e->stream, e->headw[i], (size_t)H * H); if (pm) { set_err(pm); hok = false; } }
-        }
-        hok = hok && upload_scorer(e, ht + GLC_TENSORS_HEAD);
-        if (!hok) break;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); break; }
-        ok = true;
-    } while (0);
-    (void)hipFree(staging);
-    return ok;
+        for (size_t i = 0; i < NQ; ++i) bqkv[i] = t[2][i];
+        for (size_t i = 0; i < NKV; ++i) { bqkv[NQ + i] = t[4][i]; bqkv[NQ + NKV + i] = t[6][i]; }
+        w.bqkv = upload_f32(e, bqkv.data(), NQKV);
+        w.ln1 = upload_f32(e, t[0], H); w.ln2 = upload_f32(e, t[8], H);
+        if (!w.bqkv || !w.ln1 || !w.ln2) return false;
+        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // bqkv host buffer is reused
+    }
+    e->final_norm = upload_f32(e, tensors[1 + GLC_DEC_TENSORS_PER_LAYER * L], H);
+    return e->final_norm != nullptr;
 }
 
 // ModernBERT backbone: upload + convert weights (include/gliclass_hip.h tensor order).  Per layer: Wqkv as it is (rows Q | K | V), Wo,
 // Wi (rows input | gate; interleaved 16 input / 16 gate rows when GeGLU runs in the GEMM epilogue, as the decoder's gate / up), mlp.Wo.
-bool create_modernbert(glc_engine* e, const float* const* tensors) {
+bool create_modernbert(glc_engine* e, const float* const* tensors, float* staging) {
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, I = c.inter, L = c.layers;
-    const size_t es = esize(e->dtype);
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return false; }
-    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { set_err("event create failed"); return false; }
-    size_t stage_n = (size_t)c.vocab * H;
-    if (3 * (size_t)H * H > stage_n) stage_n = 3 * (size_t)H * H;
-    if (2 * (size_t)I * H > stage_n) stage_n = 2 * (size_t)I * H;
-    float* staging = nullptr;
-    if (hipMalloc((void**)&staging, stage_n * sizeof(float)) != hipSuccess) { set_err("staging alloc failed"); return false; }
-    bool ok = false;
-    do {
-        e->emb = dmalloc(e, (size_t)c.vocab * H * es, false);
-        if (!e->emb || !upload_as(e, tensors[0], (size_t)c.vocab * H, e->emb, staging)) break;
-        e->eln_g = upload_f32(e, tensors[1], H);
-        e->zero_bias = (float*)dmalloc(e, (size_t)H * sizeof(float));
-        if (!e->eln_g || !e->zero_bias) break;
-        e->dlayers.resize(L);
-        // GeGLU in the epilogue of the staggered 256-tile GEMM when the shapes allow it (16-bit operands; fp32 mode: the group-split GEMM)
-        e->fused_swiglu = (e->dtype != GLC_F32 || (e->w_presplit && e->dec_split && H % 256 == 0)) && (2 * I) % 256 == 0 && H % 32 == 0 && I % 16 == 0 &&
-                          glc_dev_env("GLC_NO_FUSED_SWIGLU") == nullptr;
-        std::vector<float> wi_host(e->fused_swiglu ? 2 * (size_t)I * H : 0);
-        bool lok = true;
-        for (int l = 0; l < L && lok; ++l) {
-            const float* const* t = tensors + glc_mb_layer_base(l);
-            const float* attn_norm = l > 0 ? t[0] : nullptr;
-            if (l > 0) ++t;                                          // t: Wqkv Wo mlp_norm Wi Wo
-            DecLayerW& w = e->dlayers[l];
-            w.Wqkv = dmalloc(e, 3 * (size_t)H * H * es, false);
-            w.Wo = dmalloc(e, (size_t)H * H * es, false);
-            w.Wgu = dmalloc(e, 2 * (size_t)I * H * es, false);
-            w.Wd = dmalloc(e, (size_t)H * I * es, false);
-            if (!w.Wqkv || !w.Wo || !w.Wgu || !w.Wd) { lok = false; break; }
-            lok = upload_as(e, t[0], 3 * (size_t)H * H, w.Wqkv, staging) && upload_as(e, t[1], (size_t)H * H, w.Wo, staging) &&
-                  upload_as(e, t[4], (size_t)H * I, w.Wd, staging);
-            if (lok && e->fused_swiglu) {
-                // rows [32 f, 32 f + 16) = input rows of features 16 f .. 16 f + 15, rows [32 f + 16, 32 f + 32) = their gate rows
-                for (int f = 0; f < I / 16; ++f) {
-                    memcpy(wi_host.data() + (size_t)(32 * f) * H, t[3] + (size_t)(16 * f) * H, (size_t)16 * H * sizeof(float));
-                    memcpy(wi_host.data() + (size_t)(32 * f + 16) * H, t[3] + (size_t)(I + 16 * f) * H, (size_t)16 * H * sizeof(float));
-                }
-                lok = upload_as(e, wi_host.data(), 2 * (size_t)I * H, w.Wgu, staging);
-            } else if (lok) {
-                lok = upload_as(e, t[3], 2 * (size_t)I * H, w.Wgu, staging);
-            }
-            if (!lok) break;
-            if (e->w_presplit && e->dtype == GLC_F32) {     // group-split weight rows (the operand image of both split-f16 GEMM kernels)
-                const char* pm = glc_launch_presplit(e->stream, w.Wqkv, 3 * (size_t)H * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wo, (size_t)H * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wgu, 2 * (size_t)I * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wd, (size_t)H * I);
-                if (pm) { set_err(pm); lok = false; break; }
-            }
-            if (attn_norm) { w.ln1 = upload_f32(e, attn_norm, H); if (!w.ln1) { lok = false; break; } }
-            w.ln2 = upload_f32(e, t[2], H);
-            if (!w.ln2) { lok = false; break; }
-        }
-        if (!lok) break;
-        const int fin = L > 0 ? glc_mb_layer_base(L) : 2;
-        e->final_norm = upload_f32(e, tensors[fin], H);
-        if (!e->final_norm) break;
-        const float* const* ht = tensors + fin + 1;
-        bool hok = true;
-        for (int i = 0; i < 8 && hok; ++i) {
-            e->headw[i] = upload_f32(e, ht[i], (i % 2 == 0) ? (size_t)H * H : (size_t)H); hok = e->headw[i] != nullptr;
-            if (hok && (i % 2 == 0) && e->w_presplit) { const char* pm = glc_launch_presplit(e->stream, e->headw[i], (size_t)H * H); if (pm) { set_err(pm); hok = false; } }
-        }
-        hok = hok && upload_scorer(e, ht + GLC_TENSORS_HEAD);
-        if (!hok) break;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); break; }
-        ok = true;
-    } while (0);
-    (void)hipFree(staging);
-    return ok;
+    const size_t HH = (size_t)H * H, IH = (size_t)I * H;
+    e->eln_g = upload_f32(e, tensors[1], H);
+    e->zero_bias = (float*)dmalloc(e, (size_t)H * sizeof(float));
+    if (!e->eln_g || !e->zero_bias) return false;
+    e->dlayers.resize(L);
+    std::vector<float> wi_host;
+    for (int l = 0; l < L; ++l) {
+        const float* const* t = tensors + glc_mb_layer_base(l);
+        const float* attn_norm = l > 0 ? t[0] : nullptr;
+        if (l > 0) ++t;                                          // t: Wqkv Wo mlp_norm Wi Wo
+        DecLayerW& w = e->dlayers[l];
+        if (e->fused_swiglu) interleave_glu_rows(t[3], t[3] + IH, I, H, wi_host);
+        if (!upload_projections(e, staging, {{&w.Wqkv, {{t[0], 3 * HH}}}, {&w.Wo, {{t[1], HH}}}, {&w.Wgu, {{e->fused_swiglu ? wi_host.data() : t[3], 2 * IH}}},
+                                             {&w.Wd, {{t[4], IH}}}}))
+            return false;
+        if (attn_norm && !(w.ln1 = upload_f32(e, attn_norm, H))) return false;
+        if (!(w.ln2 = upload_f32(e, t[2], H))) return false;
+    }
+    e->final_norm = upload_f32(e, tensors[L > 0 ? glc_mb_layer_base(L) : 2], H);
+    return e->final_norm != nullptr;
 }
 
 // the value a 16-bit MFMA operand carries for f (host side of glc_launch_convert)
@@ -1179,6 +1113,132 @@ inline float round_as_operand(float f, int dtype) {
     if (dtype == GLC_F16) return (float)(_Float16)f;
     if (dtype == GLC_BF16) return (float)(__bf16)f;
     return f;
+}
+
+// DeBERTa-v3 backbone: upload + convert weights, the per-layer position projections and the LayerNorm folds
+bool create_deberta(glc_engine* e, const float* const* tensors, float* staging) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, L = c.layers, nh = c.heads, dtype = e->dtype;
+    const size_t HH = (size_t)H * H, IH = (size_t)I * H;
+    const int span = c.pos_buckets > 0 ? c.pos_buckets : c.max_rel_pos;
+    const int P = 2 * span;
+    e->P = P;
+    const size_t es = esize(dtype);
+    e->eln_g = upload_f32(e, tensors[1], H); e->eln_b = upload_f32(e, tensors[2], H);
+    if (!e->eln_g || !e->eln_b) return false;
+
+    // R = LayerNorm(rel_embeddings) in fp32 (HF:595-599), then to T, padded to 128 rows
+    const int Ppad = round_up(P, 256);
+    float* rel_f32 = upload_f32(e, tensors[3], (size_t)P * H);
+    float* rg = upload_f32(e, tensors[4], H); float* rb = upload_f32(e, tensors[5], H);
+    float* Rf = (float*)dmalloc(e, (size_t)Ppad * H * sizeof(float));
+    void* Rt = dmalloc(e, (size_t)Ppad * H * es);
+    void* vscratch = dmalloc(e, (size_t)nh * 64 * P * es);
+    if (!rel_f32 || !rg || !rb || !Rf || !Rt || !vscratch) return false;
+    KCHK(glc_launch_layernorm(e->stream, GLC_F32, rel_f32, Rf, rg, rb, c.ln_eps, P, H), false);
+    KCHK(glc_launch_convert(e->stream, dtype, Rf, Rt, (size_t)Ppad * H), false);
+
+    // HF:237-242: scores / sqrt(d * 3); times log2(e) so that the attention kernels can use exp2 directly
+    const float inv_scale = 1.4426950408889634f / sqrtf((float)c.head_dim * 3.0f);
+    std::vector<float> wq(HH), bqkv(3 * (size_t)H);
+    e->layers.resize(L);
+    float ln_bound = 0.f;
+    for (int i = 0; i < H; ++i) ln_bound = fmaxf(ln_bound, fabsf(tensors[1][i]) * sqrtf((float)H) + fabsf(tensors[2][i]));      // the embedding LayerNorm
+    for (int l = 0; l < L; ++l) {
+        const float* const* t = tensors + GLC_TENSORS_FIXED + GLC_TENSORS_PER_LAYER * l;
+        LayerW& w = e->layers[l];
+        w.PK = dmalloc(e, (size_t)nh * P * 64 * es);
+        w.PQ = dmalloc(e, (size_t)nh * P * 64 * es);
+        if (!w.PK || !w.PQ) return false;
+        for (size_t i = 0; i < HH; ++i) wq[i] = t[0][i] * inv_scale;   // fold log2(e)/sqrt(3d) into the query projection
+        for (int i = 0; i < H; ++i) { bqkv[i] = t[1][i] * inv_scale; bqkv[H + i] = t[3][i]; bqkv[2 * H + i] = t[5][i]; }
+        if (!upload_projections(e, staging, {{&w.Wqkv, {{wq.data(), HH}, {t[2], HH}, {t[4], HH}}}, {&w.Wo, {{t[6], HH}}}, {&w.W1, {{t[10], IH}}}, {&w.W2, {{t[12], IH}}}}))
+            return false;
+        w.bqkv = upload_f32(e, bqkv.data(), 3 * (size_t)H);
+        w.bo = upload_f32(e, t[7], H); w.ln1g = upload_f32(e, t[8], H); w.ln1b = upload_f32(e, t[9], H);
+        w.b1 = upload_f32(e, t[11], I); w.b2 = upload_f32(e, t[13], H);
+        w.ln2g = upload_f32(e, t[14], H); w.ln2b = upload_f32(e, t[15], H);
+        for (int i = 0; i < H; ++i) {       // (proactive fp8 range guard, below: the largest element a normalised row of this layer can hold)
+            ln_bound = fmaxf(ln_bound, fmaxf(fabsf(t[8][i]) * sqrtf((float)H) + fabsf(t[9][i]), fabsf(t[14][i]) * sqrtf((float)H) + fabsf(t[15][i])));
+        }
+        if (!w.bqkv || !w.bo || !w.ln1g || !w.ln1b || !w.b1 || !w.b2 || !w.ln2g || !w.ln2b) return false;
+        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // bqkv host buffer is reused
+        // position projections (HF:296-302, share_att_key): PQ = query_proj(R)*log2e/sqrt(3d), PK = key_proj(R)
+        GemmArgs g;
+        g.A = Rt; g.W = w.Wqkv; g.bias = w.bqkv; g.Qh = w.PQ; g.Kh = w.PK; g.Vt = vscratch;
+        g.Mpad = Ppad; g.N = 3 * H; g.K = H; g.Mvalid = P; g.Sp = P; g.nh = nh; g.H = H;
+        g.w_presplit = e->w_presplit && dtype == GLC_F32;
+        KCHK(glc_launch_gemm_auto(e->stream, dtype, EPI_QKV, g), false);
+        if (e->attn_split) {      // the same tables once more as split-f16 units for the fp32 band kernel
+            w.PKs = dmalloc(e, (size_t)nh * P * 64 * es);
+            w.PQs = dmalloc(e, (size_t)nh * P * 64 * es);
+            if (!w.PKs || !w.PQs) return false;
+            g.Qh = w.PQs; g.Kh = w.PKs; g.qkv_split = 1;
+            KCHK(glc_launch_gemm_auto(e->stream, dtype, EPI_QKV, g), false);
+        }
+        if (e->ln_fused && ((e->w_presplit && dtype == GLC_F32) || dtype != GLC_F32)) {
+            // LayerNorm folded into the consumer GEMMs of the group-split pipeline (GemmArgs::a_stats):
+            //   W1' = W1 diag(gamma1), c1 = W1' 1, d1 = W1 beta1 + b1            (this layer's ln1 feeds its FFN1)
+            //   Wqkv' = Wqkv diag(gamma2 of layer l - 1), cq, dq likewise          (the previous layer's ln2 feeds this QKV; layer 0
+            //   reads the embedding LayerNorm's output, which stays a kernel of its own)
+            // (upload_projections splits the folded copies in the fp32 mode; the 16-bit modes keep plain rows of T)
+            std::vector<float> wf((size_t)(I > 3 * H ? I : 3 * H) * H), cv(I > 3 * H ? I : 3 * H), dv(cv.size());
+            auto fold = [&](const float* Wsrc, int rows, const float* gam, const float* bet, const float* b0, int row0) {
+                for (int n = 0; n < rows; ++n) {
+                    double cs = 0.0, ds = 0.0;
+                    const float* wr = Wsrc + (size_t)n * H;
+                    float* o = wf.data() + (size_t)(row0 + n) * H;
+                    // c[n] sums the folded weights AS THE MFMA SEES THEM (rounded to T in the 16-bit modes; hi + lo in the fp32 mode is f to 2^-22):
+                    // summed from the unrounded values, rstd (acc - mean c[n]) would keep a residue mean rstd sum(round(W') - W')
+                    for (int k = 0; k < H; ++k) { const float f = wr[k] * gam[k]; o[k] = f; cs += (double)round_as_operand(f, dtype); ds += (double)bet[k] * (double)wr[k]; }
+                    cv[row0 + n] = (float)cs; dv[row0 + n] = (float)(ds + (double)b0[row0 + n]);
+                }
+            };
+            fold(t[10], I, t[8], t[9], t[11], 0);
+            if (!upload_projections(e, staging, {{&w.W1f, {{wf.data(), IH}}}})) return false;
+            w.c1 = upload_f32(e, cv.data(), I); w.d1 = upload_f32(e, dv.data(), I);
+            if (!w.c1 || !w.d1) return false;
+            if (l > 0) {
+                const float* const* tp = tensors + GLC_TENSORS_FIXED + GLC_TENSORS_PER_LAYER * (l - 1);
+                fold(wq.data(), H, tp[14], tp[15], bqkv.data(), 0);       // wq / bqkv still hold this layer's scaled query projection
+                fold(t[2], H, tp[14], tp[15], bqkv.data(), H);
+                fold(t[4], H, tp[14], tp[15], bqkv.data(), 2 * H);
+                if (!upload_projections(e, staging, {{&w.Wqkvf, {{wf.data(), 3 * HH}}}})) return false;
+                w.cq = upload_f32(e, cv.data(), 3 * (size_t)H); w.dq = upload_f32(e, dv.data(), 3 * (size_t)H);
+                if (!w.cq || !w.dq) return false;
+            }
+            if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // host vectors are reused
+        }
+        if (e->mx_built && w.PKs && w.PQs) {
+            // MX pipeline: the GX copies of the projection weights are built by the first forward that takes the pipeline (build_mx_weights);
+            // the position tables are converted here (small, and the range guard decides per layer at load): PQ travels as (hi8 | lo8), PK as (lo8 | hi8)
+            // (each buffer = the tile images twice: [MX steps as 32 bytes per lane — the Q / K tile format | planar: MX steps as two 16-byte planes,
+            //  every piece of a row at the SAME per-lane offset, glc_layout.h] — the band loop's requests read the second copy, round 6)
+            w.PKm = dmalloc(e, 2 * (size_t)nh * P * 64 * es);
+            w.PQm = dmalloc(e, 2 * (size_t)nh * P * 64 * es);
+            // (fp8 range guard at load: a table value beyond the e4m3 range keeps this layer's attention on split units)
+            unsigned seen = 0;
+            const char* pm = !init_range_guard(e) ? "range guard: allocation failed" : (w.PKm && w.PQm) ? glc_launch_units_to_mxt(e->stream, w.PKs, w.PKm, nh * (P / 32), 0, e->d_gxsat) : "MX position tables: allocation failed";
+            if (!pm) pm = glc_launch_units_to_mxt(e->stream, w.PQs, w.PQm, nh * (P / 32), 1, e->d_gxsat);
+            if (!pm) pm = glc_launch_units_to_mxt(e->stream, w.PKs, (unsigned char*)w.PKm + (size_t)nh * P * 64 * es, nh * (P / 32), 0, nullptr, 1);
+            if (!pm) pm = glc_launch_units_to_mxt(e->stream, w.PQs, (unsigned char*)w.PQm + (size_t)nh * P * 64 * es, nh * (P / 32), 1, nullptr, 1);
+            if (!pm && (hipMemcpyAsync(&seen, e->d_gxsat, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)) pm = "MX position tables: readback failed";
+            KCHK(pm, false);
+            if (seen != e->gxsat_seen[0]) { e->gxsat_seen[0] = seen; dfree(e, w.PKm); dfree(e, w.PQm); w.PKm = w.PQm = nullptr; }
+        }
+    }
+    // Proactive fp8 range guard: the activation rows of the MX pipeline are LayerNorm outputs (and raw sums built from
+    // them); an element of a normalised row is at most |gamma| sqrt(H) + |beta|.  A checkpoint whose gains put that bound beyond e4m3's
+    // 448 (outlier channels) starts with the activation exponent the reactive guard would reach after one repeated forward — no request
+    // pays the 2-3x repeat.  (The bound is the worst case of one spiked row; the reactive guard stays in place behind it.)
+    if (e->mx_built && ln_bound > 448.0f && e->act_sc == 0) {
+        e->act_sc = kActScLow;
+        fprintf(stderr, "gliclass: LayerNorm gains of this checkpoint allow activations up to %.0f (beyond the fp8 range of the MX operand images, 448); "
+                        "this engine's activation rows carry exponent %d (|x| up to %d) from the start\n", ln_bound, kActScLow, 448 << -kActScLow);
+    }
+    if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // (the position projections read the load-time tables)
+    dfree(e, rel_f32); dfree(e, rg); dfree(e, rb); dfree(e, Rf); dfree(e, Rt); dfree(e, vscratch);
+    return true;
 }
 
 bool check_shape(const glc_engine* e, int B, int S, int C) {
@@ -1244,6 +1304,10 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (ndev <= 0) { set_err("engine_create: no HIP device visible (this engine has no CPU path)"); return nullptr; }
     if (device < 0 || device >= ndev) { set_err("engine_create: bad device ordinal"); return nullptr; }
     HIPCHK(hipSetDevice(device), nullptr);
+    if (dec) {
+        const size_t NQ = (size_t)cfg->heads * cfg->head_dim, NKV = (size_t)(cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads) * cfg->head_dim;
+        if (NQ % 128 || NKV % 64 || (NQ + 2 * NKV) % 128) { set_err("engine_create: decoder projection widths must be multiples of 128"); return nullptr; }
+    }
 
     glc_engine* e = new glc_engine();
     e->cfg = *cfg; e->dtype = dtype; e->device = device;
@@ -1269,187 +1333,23 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     }
     if (const char* gv = glc_dev_env("GLC_GS")) { const int g = atoi(gv); e->gs_mode = g < 0 ? 0 : (g > 2 ? 2 : g); }       // developer A/B switch
     if (const char* bv = getenv("GLICLASS_LENGTH_BUCKETS")) { const int g = atoi(bv); e->max_buckets = g < 1 ? 1 : (g > 64 ? 64 : g); }
-    if (dec) {
-        if (!create_decoder(e, tensors)) { glc_engine_destroy(e); return nullptr; }
-        return e;
-    }
-    if (mb) {
-        if (!create_modernbert(e, tensors)) { glc_engine_destroy(e); return nullptr; }
-        return e;
-    }
-    const int H = cfg->hidden, I = cfg->inter, L = cfg->layers, nh = cfg->heads;
-    const int span = cfg->pos_buckets > 0 ? cfg->pos_buckets : cfg->max_rel_pos;
-    const int P = 2 * span;
-    e->P = P;
-    const size_t es = esize(dtype);
-    bool ok = false;
-    do {
-        if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); break; }
-        if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { set_err("event create failed"); break; }
-        size_t stage_n = (size_t)cfg->vocab * H;
-        if ((size_t)I * H > stage_n) stage_n = (size_t)I * H;
-        if (3 * (size_t)H * H > stage_n) stage_n = 3 * (size_t)H * H;     // the folded fused QKV weight goes up in one piece
-        float* staging = nullptr;
-        if (hipMalloc((void**)&staging, stage_n * sizeof(float)) != hipSuccess) { set_err("staging alloc failed"); break; }
-        auto fail = [&]() { (void)hipFree(staging); };
+    // decoder SwiGLU / ModernBERT GeGLU in the epilogue of the staggered 256-tile GEMM when the shapes allow it (16-bit operands; fp32 mode: the
+    // group-split 256-tile GEMM has the same epilogue, its small-forward fallback un-fuses on the interleaved columns)
+    const int H = cfg->hidden, I = cfg->inter;
+    e->fused_swiglu = (dec || mb) && (dtype != GLC_F32 || (e->w_presplit && e->dec_split && H % 256 == 0)) && (2 * I) % 256 == 0 && H % 32 == 0 &&
+                      I % 16 == 0 && glc_dev_env("GLC_NO_FUSED_SWIGLU") == nullptr;
 
-        // embeddings (HF:518-562)
-        e->emb = dmalloc(e, (size_t)cfg->vocab * H * es, false);
-        if (!e->emb || !upload_as(e, tensors[0], (size_t)cfg->vocab * H, e->emb, staging)) { fail(); break; }
-        e->eln_g = upload_f32(e, tensors[1], H); e->eln_b = upload_f32(e, tensors[2], H);
-        if (!e->eln_g || !e->eln_b) { fail(); break; }
-
-        // R = LayerNorm(rel_embeddings) in fp32 (HF:595-599), then to T, padded to 128 rows
-        const int Ppad = round_up(P, 256);
-        float* rel_f32 = upload_f32(e, tensors[3], (size_t)P * H);
-        float* rg = upload_f32(e, tensors[4], H); float* rb = upload_f32(e, tensors[5], H);
-        float* Rf = (float*)dmalloc(e, (size_t)Ppad * H * sizeof(float));
-        void* Rt = dmalloc(e, (size_t)Ppad * H * es);
-        void* vscratch = dmalloc(e, (size_t)nh * 64 * P * es);
-        if (!rel_f32 || !rg || !rb || !Rf || !Rt || !vscratch) { fail(); break; }
-        const char* m = glc_launch_layernorm(e->stream, GLC_F32, rel_f32, Rf, rg, rb, cfg->ln_eps, P, H);
-        if (!m) m = glc_launch_convert(e->stream, dtype, Rf, Rt, (size_t)Ppad * H);
-        if (m) { set_err(m); fail(); break; }
-
-        // HF:237-242: scores / sqrt(d * 3); times log2(e) so that the attention kernels can use exp2 directly
-        const float inv_scale = 1.4426950408889634f / sqrtf((float)cfg->head_dim * 3.0f);
-        std::vector<float> wq((size_t)H * H), bq(H), bqkv(3 * (size_t)H);
-        e->layers.resize(L);
-        bool lok = true;
-        float ln_bound = 0.f;
-        for (int i = 0; i < H; ++i) ln_bound = fmaxf(ln_bound, fabsf(tensors[1][i]) * sqrtf((float)H) + fabsf(tensors[2][i]));      // the embedding LayerNorm
-        for (int l = 0; l < L && lok; ++l) {
-            const float* const* t = tensors + GLC_TENSORS_FIXED + GLC_TENSORS_PER_LAYER * l;
-            LayerW& w = e->layers[l];
-            w.Wqkv = dmalloc(e, 3 * (size_t)H * H * es, false);
-            w.Wo = dmalloc(e, (size_t)H * H * es, false);
-            w.W1 = dmalloc(e, (size_t)I * H * es, false);
-            w.W2 = dmalloc(e, (size_t)H * I * es, false);
-            w.PK = dmalloc(e, (size_t)nh * P * 64 * es);
-            w.PQ = dmalloc(e, (size_t)nh * P * 64 * es);
-            if (!w.Wqkv || !w.Wo || !w.W1 || !w.W2 || !w.PK || !w.PQ) { lok = false; break; }
-            for (size_t i = 0; i < (size_t)H * H; ++i) wq[i] = t[0][i] * inv_scale;   // fold log2(e)/sqrt(3d) into the query projection
-            for (int i = 0; i < H; ++i) { bqkv[i] = t[1][i] * inv_scale; bqkv[H + i] = t[3][i]; bqkv[2 * H + i] = t[5][i]; }
-            lok = upload_as(e, wq.data(), (size_t)H * H, w.Wqkv, staging) &&
-                  upload_as(e, t[2], (size_t)H * H, (char*)w.Wqkv + (size_t)H * H * es, staging) &&
-                  upload_as(e, t[4], (size_t)H * H, (char*)w.Wqkv + 2 * (size_t)H * H * es, staging) &&
-                  upload_as(e, t[6], (size_t)H * H, w.Wo, staging) && upload_as(e, t[10], (size_t)I * H, w.W1, staging) &&
-                  upload_as(e, t[12], (size_t)H * I, w.W2, staging);
-            if (!lok) break;
-            w.bqkv = upload_f32(e, bqkv.data(), 3 * (size_t)H);
-            w.bo = upload_f32(e, t[7], H); w.ln1g = upload_f32(e, t[8], H); w.ln1b = upload_f32(e, t[9], H);
-            w.b1 = upload_f32(e, t[11], I); w.b2 = upload_f32(e, t[13], H);
-            w.ln2g = upload_f32(e, t[14], H); w.ln2b = upload_f32(e, t[15], H);
-            for (int i = 0; i < H; ++i) {       // (proactive fp8 range guard, below: the largest element a normalised row of this layer can hold)
-                ln_bound = fmaxf(ln_bound, fmaxf(fabsf(t[8][i]) * sqrtf((float)H) + fabsf(t[9][i]), fabsf(t[14][i]) * sqrtf((float)H) + fabsf(t[15][i])));
-            }
-            if (!w.bqkv || !w.bo || !w.ln1g || !w.ln1b || !w.b1 || !w.b2 || !w.ln2g || !w.ln2b) { lok = false; break; }
-            if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); lok = false; break; }   // bqkv host buffer is reused
-            if (e->w_presplit && dtype == GLC_F32) {
-                const char* pm = glc_launch_presplit(e->stream, w.Wqkv, 3 * (size_t)H * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.Wo, (size_t)H * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.W1, (size_t)I * H);
-                if (!pm) pm = glc_launch_presplit(e->stream, w.W2, (size_t)H * I);
-                if (pm) { set_err(pm); lok = false; break; }
-            }
-            // position projections (HF:296-302, share_att_key): PQ = query_proj(R)*log2e/sqrt(3d), PK = key_proj(R)
-            GemmArgs g;
-            g.A = Rt; g.W = w.Wqkv; g.bias = w.bqkv; g.Qh = w.PQ; g.Kh = w.PK; g.Vt = vscratch;
-            g.Mpad = Ppad; g.N = 3 * H; g.K = H; g.Mvalid = P; g.Sp = P; g.nh = nh; g.H = H;
-            g.w_presplit = e->w_presplit && dtype == GLC_F32;
-            const char* gm = glc_launch_gemm_auto(e->stream, dtype, EPI_QKV, g);
-            if (gm) { set_err(gm); lok = false; }
-            if (lok && e->attn_split) {      // the same tables once more as split-f16 units for the fp32 band kernel
-                w.PKs = dmalloc(e, (size_t)nh * P * 64 * es);
-                w.PQs = dmalloc(e, (size_t)nh * P * 64 * es);
-                if (!w.PKs || !w.PQs) { lok = false; break; }
-                g.Qh = w.PQs; g.Kh = w.PKs; g.qkv_split = 1;
-                gm = glc_launch_gemm_auto(e->stream, dtype, EPI_QKV, g);
-                if (gm) { set_err(gm); lok = false; }
-            }
-            if (lok && e->ln_fused && ((e->w_presplit && dtype == GLC_F32) || dtype != GLC_F32)) {
-                // LayerNorm folded into the consumer GEMMs of the group-split pipeline (GemmArgs::a_stats):
-                //   W1' = W1 diag(gamma1), c1 = W1' 1, d1 = W1 beta1 + b1            (this layer's ln1 feeds its FFN1)
-                //   Wqkv' = Wqkv diag(gamma2 of layer l - 1), cq, dq likewise          (the previous layer's ln2 feeds this QKV; layer 0
-                //   reads the embedding LayerNorm's output, which stays a kernel of its own)
-                std::vector<float> wf((size_t)(I > 3 * H ? I : 3 * H) * H), cv(I > 3 * H ? I : 3 * H), dv(cv.size());
-                auto fold = [&](const float* Wsrc, int rows, const float* gam, const float* bet, const float* b0, int row0) {
-                    for (int n = 0; n < rows; ++n) {
-                        double cs = 0.0, ds = 0.0;
-                        const float* wr = Wsrc + (size_t)n * H;
-                        float* o = wf.data() + (size_t)(row0 + n) * H;
-                        // c[n] sums the folded weights AS THE MFMA SEES THEM (rounded to T in the 16-bit modes; hi + lo in the fp32 mode is f to 2^-22):
-                        // summed from the unrounded values, rstd (acc - mean c[n]) would keep a residue mean rstd sum(round(W') - W')
-                        for (int k = 0; k < H; ++k) { const float f = wr[k] * gam[k]; o[k] = f; cs += (double)round_as_operand(f, dtype); ds += (double)bet[k] * (double)wr[k]; }
-                        cv[row0 + n] = (float)cs; dv[row0 + n] = (float)(ds + (double)b0[row0 + n]);
-                    }
-                };
-                fold(t[10], I, t[8], t[9], t[11], 0);
-                w.W1f = dmalloc(e, (size_t)I * H * es, false);
-                if (!w.W1f || !upload_as(e, wf.data(), (size_t)I * H, w.W1f, staging)) { lok = false; break; }
-                const char* pm = dtype == GLC_F32 ? glc_launch_presplit(e->stream, w.W1f, (size_t)I * H) : nullptr;     // (16-bit modes: plain rows of T)
-                if (pm) { set_err(pm); lok = false; break; }
-                w.c1 = upload_f32(e, cv.data(), I); w.d1 = upload_f32(e, dv.data(), I);
-                if (!w.c1 || !w.d1) { lok = false; break; }
-                if (l > 0) {
-                    const float* const* tp = tensors + GLC_TENSORS_FIXED + GLC_TENSORS_PER_LAYER * (l - 1);
-                    fold(wq.data(), H, tp[14], tp[15], bqkv.data(), 0);       // wq / bqkv still hold this layer's scaled query projection
-                    fold(t[2], H, tp[14], tp[15], bqkv.data(), H);
-                    fold(t[4], H, tp[14], tp[15], bqkv.data(), 2 * H);
-                    w.Wqkvf = dmalloc(e, 3 * (size_t)H * H * es, false);
-                    if (!w.Wqkvf || !upload_as(e, wf.data(), 3 * (size_t)H * H, w.Wqkvf, staging)) { lok = false; break; }
-                    pm = dtype == GLC_F32 ? glc_launch_presplit(e->stream, w.Wqkvf, 3 * (size_t)H * H) : nullptr;
-                    if (pm) { set_err(pm); lok = false; break; }
-                    w.cq = upload_f32(e, cv.data(), 3 * (size_t)H); w.dq = upload_f32(e, dv.data(), 3 * (size_t)H);
-                    if (!w.cq || !w.dq) { lok = false; break; }
-                }
-                if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); lok = false; break; }   // host vectors are reused
-            }
-            if (lok && e->mx_built) {
-                // MX pipeline: the GX copies of the projection weights are built by the first forward that takes the pipeline (build_mx_weights);
-                // the position tables are converted here (small, and the range guard decides per layer at load)
-                if (lok && w.PKs && w.PQs) {      // the position tables as MX tiles: PQ travels as (hi8 | lo8), PK as (lo8 | hi8)
-                    // (each buffer = the tile images twice: [MX steps as 32 bytes per lane — the Q / K tile format | planar: MX steps as two 16-byte planes,
-                    //  every piece of a row at the SAME per-lane offset, glc_layout.h] — the band loop's requests read the second copy, round 6)
-                    w.PKm = dmalloc(e, 2 * (size_t)nh * P * 64 * es);
-                    w.PQm = dmalloc(e, 2 * (size_t)nh * P * 64 * es);
-                    // (fp8 range guard at load: a table value beyond the e4m3 range keeps this layer's attention on split units)
-                    unsigned seen = 0;
-                    const char* pm = !init_range_guard(e) ? "range guard: allocation failed" : (w.PKm && w.PQm) ? glc_launch_units_to_mxt(e->stream, w.PKs, w.PKm, nh * (P / 32), 0, e->d_gxsat) : "MX position tables: allocation failed";
-                    if (!pm) pm = glc_launch_units_to_mxt(e->stream, w.PQs, w.PQm, nh * (P / 32), 1, e->d_gxsat);
-                    if (!pm) pm = glc_launch_units_to_mxt(e->stream, w.PKs, (unsigned char*)w.PKm + (size_t)nh * P * 64 * es, nh * (P / 32), 0, nullptr, 1);
-                    if (!pm) pm = glc_launch_units_to_mxt(e->stream, w.PQs, (unsigned char*)w.PQm + (size_t)nh * P * 64 * es, nh * (P / 32), 1, nullptr, 1);
-                    if (!pm && (hipMemcpyAsync(&seen, e->d_gxsat, sizeof(unsigned), hipMemcpyDeviceToHost, e->stream) != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)) pm = "MX position tables: readback failed";
-                    if (pm) { set_err(pm); lok = false; }
-                    else if (seen != e->gxsat_seen[0]) { e->gxsat_seen[0] = seen; dfree(e, w.PKm); dfree(e, w.PQm); w.PKm = w.PQm = nullptr; }
-                }
-                if (!lok) break;
-            }
-        }
-        if (!lok) { fail(); break; }
-        // Proactive fp8 range guard: the activation rows of the MX pipeline are LayerNorm outputs (and raw sums built from
-        // them); an element of a normalised row is at most |gamma| sqrt(H) + |beta|.  A checkpoint whose gains put that bound beyond e4m3's
-        // 448 (outlier channels) starts with the activation exponent the reactive guard would reach after one repeated forward — no request
-        // pays the 2-3x repeat.  (The bound is the worst case of one spiked row; the reactive guard stays in place behind it.)
-        if (e->mx_built && ln_bound > 448.0f && e->act_sc == 0) {
-            e->act_sc = kActScLow;
-            fprintf(stderr, "gliclass: LayerNorm gains of this checkpoint allow activations up to %.0f (beyond the fp8 range of the MX operand images, 448); "
-                            "this engine's activation rows carry exponent %d (|x| up to %d) from the start\n", ln_bound, kActScLow, 448 << -kActScLow);
-        }
-        const float* const* ht = tensors + GLC_TENSORS_FIXED + GLC_TENSORS_PER_LAYER * L;
-        bool hok = true;
-        for (int i = 0; i < 8 && hok; ++i) {
-            e->headw[i] = upload_f32(e, ht[i], (i % 2 == 0) ? (size_t)H * H : (size_t)H); hok = e->headw[i] != nullptr;
-            if (hok && (i % 2 == 0) && e->w_presplit) { const char* pm = glc_launch_presplit(e->stream, e->headw[i], (size_t)H * H); if (pm) { set_err(pm); hok = false; } }
-        }
-        hok = hok && upload_scorer(e, ht + GLC_TENSORS_HEAD);
-        if (!hok) { fail(); break; }
-        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); fail(); break; }
-        (void)hipFree(staging);
-        dfree(e, rel_f32); dfree(e, rg); dfree(e, rb); dfree(e, Rf); dfree(e, Rt); dfree(e, vscratch);
-        ok = true;
-    } while (0);
-    if (!ok) { glc_engine_destroy(e); return nullptr; }
+    float* staging = nullptr;      // host f32 -> device T goes through it (upload_as)
+    struct StagingGuard { float*& p; ~StagingGuard() { (void)hipFree(p); } } staging_guard{staging};      // (every exit path)
+    auto fail = [e]() -> glc_engine* { glc_engine_destroy(e); return nullptr; };
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return fail(); }
+    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { set_err("event create failed"); return fail(); }
+    if (hipMalloc((void**)&staging, staging_floats(e->cfg) * sizeof(float)) != hipSuccess) { set_err("staging alloc failed"); return fail(); }
+    const size_t nemb = (size_t)cfg->vocab * H;           // the token embeddings (HF:518-562)
+    e->emb = dmalloc(e, nemb * esize(dtype), false);
+    if (!e->emb || !upload_as(e, tensors[0], nemb, e->emb, staging)) return fail();
+    const bool loaded = dec ? create_decoder(e, tensors, staging) : mb ? create_modernbert(e, tensors, staging) : create_deberta(e, tensors, staging);
+    if (!loaded || !upload_head(e, tensors + n_tensors - GLC_TENSORS_HEAD - glc_num_scorer_tensors(cfg->scorer))) return fail();
     return e;
 }
 
