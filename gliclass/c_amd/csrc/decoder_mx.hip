@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
 // vector-memory path — 4096 cycles per tile round of 8 waves against 2048 of matrix pipe: the path, not the pipe, bounds it.  The four waves
 // of a workgroup are four consecutive query tiles of ONE query head, so they walk the same K / V^T tiles: here each tile is fetched once
 // per workgroup by LDS-DMA (8 one-KiB pieces per wave and tile instead of 32 loads) into two-slot rings (K 2 x 16 KiB, V^T 2 x 16 KiB at
-// head_dim 128; two workgroups per CU) and read as fragments by all four, with the protocol of attention_mx2.hip: ONE workgroup barrier per
+// head_dim 128; two workgroups per CU) and read as fragments by all four.  The rings take ONE workgroup barrier per
 // key tile — after barrier(t) every wave holds its K(t) fragments and has left V^T(t - 1), so V^T(t + 1) and K(t + 2) are requested there, each
 // wave waits for its own pieces right before barrier(t + 1), which publishes them.  Causal: a wave's query tile ends the walk at its own
 // diagonal; waves that are done (or have no tile, or a padding-only one) keep moving their pieces and meeting the barriers until the

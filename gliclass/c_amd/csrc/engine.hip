@@ -136,9 +136,6 @@ struct glc_engine {
     std::map<int, int2*> mtabs;                // Sp -> the MX band kernel's ready-made row offsets (round 6; fp32 mode only): glc_kernels.h AttnArgs::mtab
     std::map<int, int2*> otabs;                // Sp -> byte offsets of the PQ / PK rows per relative distance (band kernel, 16-bit)
     std::map<int, std::pair<int, int>> dsat;   // Sp -> (rsat_pos, rsat_neg)
-    std::map<int, std::pair<void*, int4*>> mx2tabs;   // Sp -> (idx16, tinfo) of attention_mx2.hip; (null, null): this table keeps the band kernel
-    bool mx2 = false;                          // MX attention on the bucket-space kernel (attention_mx2.hip; needs its tables) instead of the band kernel (attention_mx.hip): opt-in
-                                               // (GLC_ATTN_MX2=1, glc_debug_set_mx2) — measured 4-5 % slower at c3 (docs/LOG_r01-r05.md §3f)
     // last forward
     int lastB = 0, lastS = 0, lastSp = 0;
     // debug
@@ -304,16 +301,6 @@ bool build_position_tables(glc_engine* e, int Sp) {
     for (int r = Sp - 1; r >= -(Sp - 1) && t[r + Sp - 1] == 2 * (c.pos_buckets > 0 ? c.pos_buckets : c.max_rel_pos) - 1; --r) rp = r;
     for (int r = -(Sp - 1); r <= Sp - 1 && t[r + Sp - 1] == 0; ++r) rn = r;
     e->dsat[Sp] = std::make_pair(rp, rn);
-    // tables of the bucket-space MX attention (attention_mx2.hip); a table without the structure it needs keeps the band kernel
-    std::vector<unsigned char> idx16;
-    std::vector<int4> tinfo;
-    void* d_idx = nullptr; int4* d_ti = nullptr;
-    if (e->dtype == GLC_F32 && glc_mx2_build_tables(Sp, e->P, t.data(), idx16, tinfo)) {
-        d_idx = upload_table(e, idx16, "mx2 table");
-        d_ti = d_idx ? upload_table(e, tinfo, "mx2 table") : nullptr;
-        if (!d_ti) return false;
-    }
-    e->mx2tabs[Sp] = std::make_pair(d_idx, d_ti);
     e->dtabs[Sp] = d;
     return true;
 }
@@ -891,9 +878,8 @@ bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask,
         static const bool nosat = glc_dev_env("GLC_ATTN_NOSAT") != nullptr;      // A/B switch (developer)
         if (!nosat) { a.rsat_pos = e->dsat[Sp].first; a.rsat_neg = e->dsat[Sp].second; }
         a.otab = e->otabs[Sp]; a.mtab = e->mtabs.count(Sp) ? e->mtabs[Sp] : nullptr;
-        if (mxa) { a.PK = w.PKm; a.PQ = w.PQm; e->last_mx_attn = true; a.idx16 = e->mx2tabs[Sp].first; a.tinfo = e->mx2tabs[Sp].second; }
-        const bool mxa2 = mxa && e->mx2 && a.idx16 && a.tinfo;      // bucket-space kernel (round 4) when this length's table has the structure it needs
-        { Prof p(e, PC_ATTN); KCHK(mxa2 ? glc_launch_attention_mx2(st, a) : mxa ? glc_launch_attention_mx(st, a) : launch_band(a), false); }
+        if (mxa) { a.PK = w.PKm; a.PQ = w.PQm; e->last_mx_attn = true; }
+        { Prof p(e, PC_ATTN); KCHK(mxa ? glc_launch_attention_mx(st, a) : launch_band(a), false); }
         if (e->debug_stop == 10 * l + 1) return true;
         GemmArgs o;
         o.A = e->CTX; o.W = w.Wo; o.bias = w.bo; o.C = e->T1; o.resid = e->X; o.Mpad = Mpad; o.N = H; o.K = H;
@@ -1329,7 +1315,6 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
         e->mx = e->mx_built && !(mv && !strcmp(mv, "build"));
         if (const char* av = glc_dev_env("GLC_MX_ATTN")) e->mx_attn = atoi(av) != 0;      // developer A/B switch
         if (const char* av = glc_dev_env("GLC_DEC_ROPE_EPI")) e->dec_rope_epi = atoi(av) != 0;      // developer A/B switch
-        if (const char* av = glc_dev_env("GLC_ATTN_MX2")) e->mx2 = atoi(av) != 0;         // developer A/B switch: 1 = the bucket-space kernel (attention_mx2.hip)
     }
     if (const char* gv = glc_dev_env("GLC_GS")) { const int g = atoi(gv); e->gs_mode = g < 0 ? 0 : (g > 2 ? 2 : g); }       // developer A/B switch
     if (const char* bv = getenv("GLICLASS_LENGTH_BUCKETS")) { const int g = atoi(bv); e->max_buckets = g < 1 ? 1 : (g > 64 ? 64 : g); }
@@ -1584,13 +1569,6 @@ int glc_debug_fp8_range_retries(const glc_engine* e) { return e ? e->fp8_retries
 int glc_debug_fp8_range_sticky(const glc_engine* e) { return e ? (e->fp8_sticky_off ? 1 : 0) : -1; }
 int glc_debug_activation_exponent(const glc_engine* e) { return e ? e->act_sc : 1; }
 long long glc_debug_mx_weight_bytes(const glc_engine* e) { return e ? (long long)e->mx_bytes : -1; }
-int glc_debug_set_mx2(glc_engine* e, int on) {
-    if (!e) return -1;
-#ifndef GLC_DEVELOPER
-    if (on) { set_err("set_mx2: the bucket-space attention kernel exists in developer builds only (make DEV=1)"); return -1; }
-#endif
-    std::lock_guard<std::mutex> lk(e->mu); e->mx2 = on != 0; return 0;
-}
 
 int glc_engine_set_length_buckets(glc_engine* e, int max_groups) {
     if (!e || max_groups < 1 || max_groups > 64) { set_err("set_length_buckets: 1..64 groups"); return -1; }
@@ -1806,17 +1784,14 @@ int glc_debug_get_hidden(glc_engine* e, int which, float* out, size_t out_elems)
  * which: 0 = auto (256-tile when possible), 1 = force the 128x128 kernel.  Returns ms per launch or <0. */
 float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iters, int which) {
     // which == 6: the group-split fp32-mode kernel (rows of [32 hi | 32 lo] f16 groups, 4 bytes per element; any engine dtype)
-    const int epi_abl = which / 1000;          // which = 1000 abl + 100 (1 + prio) + 9: timing ablations of the GX-row epilogue (GemmArgs::epi_abl)
-    which %= 1000;
     const int which_in = which;
     if (which >= 100) which %= 100;
-    if (which == 14) { set_err("gemm_bench: the one-wave-per-SIMD 128 x 128 wave tile (which = 14) was deleted in round 5 (docs/LOG_r01-r05.md section 9)"); return -1.f; }
-    const bool z16b = which == 13;                    // the GX kernel with the 16 x 16 MFMA shapes
-    const bool gyb = which == 11 || which == 12;      // the same kernel on GY rows (e2m3 parts with block scales); 12: plus one stamped launch
-    const bool mxb = which == 9 || which == 10 || gyb || z16b;      // the MX cross-term kernel on GX rows (gemm256x.hip); 10: plus one stamped launch
+    const bool mxb = which == 9;                      // the MX cross-term kernel on GX rows (gemm256x.hip); which = 100 (1 + prio) + 9: wave priority policy prio
     const bool gsb = which == 6 || which == 8 || mxb;
     const int mx_ws = glc_gx_weight_exponent(0.5f);
-    if (!e || M <= 0 || N <= 0 || K <= 0 || iters <= 0 || (e->dtype == GLC_F32 && !gsb) || epi < EPI_BIAS || epi > EPI_RESID) { set_err("gemm_bench: bad args"); return -1.f; }
+    if (!e || M <= 0 || N <= 0 || K <= 0 || iters <= 0 || which_in >= 1000 || (which >= 10 && which <= 14) || (e->dtype == GLC_F32 && !gsb) || epi < EPI_BIAS || epi > EPI_RESID) {
+        set_err("gemm_bench: bad args"); return -1.f;
+    }
     if (M % 256 || N % 256 || K % 64) { set_err("gemm_bench: M,N %256, K %64 required"); return -1.f; }
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device), -1.f);
@@ -1836,18 +1811,14 @@ float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iter
         if (gsb) {      // fp32 values, split in place into the group-split image (or the GX image)
             if (hipMemcpyAsync(A, tmp, nA * 4, hipMemcpyDeviceToDevice, e->stream) || hipMemcpyAsync(W, tmp, nW * 4, hipMemcpyDeviceToDevice, e->stream) ||
                 hipMemcpyAsync(R, tmp, nC * 4, hipMemcpyDeviceToDevice, e->stream)) { set_err("gemm_bench: copy failed"); break; }
-            if (gyb ? (glc_launch_to_gy(e->stream, tmp, A, M, K, 0) || glc_launch_to_gy(e->stream, tmp, W, N, K, 1) || glc_launch_to_gy(e->stream, tmp, R, M, N, 0)) :
-                mxb ? (glc_launch_to_gx(e->stream, A, nA, 0, 0) || glc_launch_to_gx(e->stream, W, nW, mx_ws, 1) || glc_launch_to_gx(e->stream, R, nC, 0, 0))
+            if (mxb ? (glc_launch_to_gx(e->stream, A, nA, 0, 0) || glc_launch_to_gx(e->stream, W, nW, mx_ws, 1) || glc_launch_to_gx(e->stream, R, nC, 0, 0))
                     : (glc_launch_presplit(e->stream, A, nA) || glc_launch_presplit(e->stream, W, nW) || glc_launch_presplit(e->stream, R, nC))) { set_err("gemm_bench: split failed"); break; }
         } else
         if (glc_launch_convert(e->stream, e->dtype, tmp, A, nA) || glc_launch_convert(e->stream, e->dtype, tmp, W, nW) ||
             glc_launch_convert(e->stream, e->dtype, tmp, R, nC)) { set_err("gemm_bench: convert failed"); break; }
         if (hipMemcpyAsync(bias, tmp, N * sizeof(float), hipMemcpyDeviceToDevice, e->stream)) break;
         GemmArgs g; g.A = A; g.W = W; g.bias = bias; g.C = C; g.resid = R; g.Mpad = M; g.N = N; g.K = K; g.mx_ws = mx_ws;
-        if (mxb && which_in >= 100) g.prio_mode = which_in / 100 - 1;      // which = 100 (1 + prio) + 9 | 10
-        g.epi_abl = mxb ? epi_abl : 0;
-        g.gy = gyb ? 1 : 0;
-        g.z16 = z16b ? 1 : 0;
+        if (mxb && which_in >= 100) g.prio_mode = which_in / 100 - 1;      // which = 100 (1 + prio) + 9
         const char* m = nullptr;
         auto launch = [&]() -> const char* { return mxb ? glc_launch_gemm256x(e->stream, epi, g) : gsb ? glc_launch_gemm256s_gs(e->stream, epi, g) : which == 1 ? glc_launch_gemm(e->stream, e->dtype, epi, g) : (which == 5 || which == 7) ? glc_launch_gemm256s(e->stream, e->dtype, epi, g) : glc_launch_gemm_auto(e->stream, e->dtype, epi, g); };
         for (int i = 0; i < 2 && !m; ++i) m = launch();
@@ -1858,13 +1829,13 @@ float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iter
         float t = 0.f;
         if (hipEventElapsedTime(&t, e->t0, e->t1)) break;
         ms = t / iters;
-        if (which == 7 || which == 8 || which == 10 || which == 12) {     // diagnostic: one stamped launch of the full-line 256-tile kernel (7: 16-bit operands, 8: group-split), EPI_BIAS
+        if (which == 7 || which == 8) {     // diagnostic: one stamped launch of the full-line 256-tile kernel (7: 16-bit operands, 8: group-split), EPI_BIAS
             unsigned long long* dbuf = nullptr;
             const size_t ns = 64 * 8 * 14;
             if (hipMalloc((void**)&dbuf, ns * sizeof(unsigned long long)) == hipSuccess) {
                 (void)hipMemsetAsync(dbuf, 0, ns * sizeof(unsigned long long), e->stream);
                 GemmArgs gd = g; gd.stamps = dbuf;
-                const char* dm = (which == 10 || which == 12) ? glc_launch_gemm256x(e->stream, EPI_BIAS, gd) : which == 8 ? glc_launch_gemm256s_gs(e->stream, EPI_BIAS, gd) : glc_launch_gemm256s(e->stream, e->dtype, EPI_BIAS, gd);
+                const char* dm = which == 8 ? glc_launch_gemm256s_gs(e->stream, EPI_BIAS, gd) : glc_launch_gemm256s(e->stream, e->dtype, EPI_BIAS, gd);
                 (void)hipStreamSynchronize(e->stream);
                 std::vector<unsigned long long> hs(ns);
                 if (!dm && hipMemcpy(hs.data(), dbuf, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1873,7 +1844,7 @@ float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iter
                         for (int b = 0; b < 64; ++b) for (int w = 4 * grp; w < 4 * grp + 4; ++w) for (int k = 0; k < 12; ++k) sg[k] += (double)hs[((size_t)b * 8 + w) * 12 + k];
                         const double n = 64 * 4, ng = sg[11] / n > 0 ? sg[11] / n : 1;
                         fprintf(stderr, "[gemm256s stamps M=%d N=%d K=%d %s, waves %d-%d] cycles per group and wave: E: dma %.0f reads+wait %.0f barrier %.0f mfma %.0f barrier %.0f | "
-                                        "O: (dma %.0f) reads+wait %.0f barrier %.0f mfma %.0f barrier %.0f | total %.0f | clock %.0f MHz\n", M, N, K, which == 12 ? "MX on GY rows" : which == 10 ? "MX" : which == 8 ? "group-split" : "16-bit", 4 * grp, 4 * grp + 3,
+                                        "O: (dma %.0f) reads+wait %.0f barrier %.0f mfma %.0f barrier %.0f | total %.0f | clock %.0f MHz\n", M, N, K, which == 8 ? "group-split" : "16-bit", 4 * grp, 4 * grp + 3,
                                 sg[0] / n / ng, sg[1] / n / ng, sg[2] / n / ng, sg[3] / n / ng, sg[4] / n / ng, sg[5] / n / ng, sg[6] / n / ng, sg[7] / n / ng, sg[8] / n / ng, sg[9] / n / ng,
                                 (sg[0] + sg[1] + sg[2] + sg[3] + sg[4] + sg[5] + sg[6] + sg[7] + sg[8] + sg[9]) / n / ng, sg[10] / n / 10.0);
                     }
@@ -1897,12 +1868,6 @@ float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iter
  * out[0] = max |mx - gs|, out[1] = max |gs|, out[2] = rms(mx - gs), out[3] = rms(gs) over the decoded outputs (mode 2: + the ln_part
  * sums in out[4] = max |diff|).  Returns 0 or < 0. */
 int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, float w_amp, int mode, double* out) {
-    if (mode >= 30) { set_err("gemm_mx_check: mode + 30 (the one-wave-per-SIMD 128 x 128 wave tile) was deleted in round 5 (docs/LOG_r01-r05.md section 9)"); return -1; }
-    const bool z16 = mode >= 20;         // mode + 20: the MX leg's main loop on the 16 x 16 MFMA shapes (GemmArgs::z16)
-    if (z16) mode -= 20;
-    const bool gy = mode >= 10;          // mode + 10: the MX leg on GY rows (e2m3 parts with block scales) instead of GX rows
-    if (gy) mode -= 10;
-    if (gy && (K % 64 || N % 64)) { set_err("gemm_mx_check: GY rows need K, N % 64 == 0"); return -1; }
     if (!e || !out || M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 32 || mode < 0 || mode > 4) { set_err("gemm_mx_check: bad args"); return -1; }
     if (mode == 4 && (N % 768 || M % 256)) { set_err("gemm_mx_check: the QKV mode needs N = 3 H, H % 256 == 0"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1910,10 +1875,8 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
     const size_t nA = (size_t)M * K, nW = (size_t)N * K, nC = (size_t)M * N;
     float *A = nullptr, *W = nullptr, *A2 = nullptr, *W2 = nullptr, *C0 = nullptr, *C1 = nullptr, *R0 = nullptr, *R1 = nullptr, *bias = nullptr, *lnc = nullptr, *gam = nullptr, *bet = nullptr;
     float2 *st = nullptr, *lp0 = nullptr, *lp1 = nullptr;
-    void *Ay = nullptr, *Wy = nullptr, *Ry = nullptr, *Cy = nullptr;
     int rc = -1;
     do {
-        if (gy && (hipMalloc(&Ay, nA * 4) || hipMalloc(&Wy, nW * 4) || hipMalloc(&Ry, nC * 4) || hipMalloc(&Cy, nC * 4))) { set_err("gemm_mx_check: alloc failed"); break; }
         if (hipMalloc((void**)&A, nA * 4) || hipMalloc((void**)&W, nW * 4) || hipMalloc((void**)&A2, nA * 4) || hipMalloc((void**)&W2, nW * 4) ||
             hipMalloc((void**)&C0, nC * 4) || hipMalloc((void**)&C1, nC * 4) || hipMalloc((void**)&R0, nC * 4) || hipMalloc((void**)&R1, nC * 4) ||
             hipMalloc((void**)&bias, (size_t)N * 4) || hipMalloc((void**)&lnc, (size_t)N * 4) || hipMalloc((void**)&gam, (size_t)N * 4) || hipMalloc((void**)&bet, (size_t)N * 4) ||
@@ -1941,15 +1904,9 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
         const char* m = glc_launch_presplit(e->stream, A, nA);
         if (!m) m = glc_launch_presplit(e->stream, W, nW);
         if (!m) m = glc_launch_presplit(e->stream, R0, nC);
-        if (gy) {
-            if (!m) m = glc_launch_to_gy(e->stream, A2, Ay, M, K, 0);
-            if (!m) m = glc_launch_to_gy(e->stream, W2, Wy, N, K, 1);
-            if (!m) m = glc_launch_to_gy(e->stream, R1, Ry, M, N, 0);
-        } else {
         if (!m) m = glc_launch_to_gx(e->stream, A2, nA, 0, 0);
         if (!m) m = glc_launch_to_gx(e->stream, W2, nW, ws, 1);
         if (!m) m = glc_launch_to_gx(e->stream, R1, nC, 0, 0);
-        }
         GemmArgs g; g.bias = bias; g.Mpad = M; g.N = N; g.K = K;
         int epi = EPI_BIAS;
         if (mode == 0) g.gs_c_plain = 1;
@@ -1962,11 +1919,7 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
         if (!m) m = glc_launch_gemm256s_gs(e->stream, epi, g);
         g.A = A2; g.W = W2; g.C = C1; g.resid = R1; g.mx_ws = ws; if (mode == 2) g.ln_part = lp1;
         if (mode == 4) { g.Qh = C1; g.Kh = C1 + third; g.Vt = C1 + 2 * third; }
-        const bool rows_out = mode == 1 || mode == 2;
-        if (gy) { g.gy = 1; g.A = Ay; g.W = Wy; g.resid = Ry; if (rows_out) g.C = Cy; }
-        g.z16 = z16 ? 1 : 0;
         if (!m) m = glc_launch_gemm256x(e->stream, epi, g);
-        if (gy && rows_out && !m) m = glc_launch_gy_to_f32(e->stream, Cy, C1, M, N);        // (the GY output rows decoded on the device)
         if (m) { set_err(m); break; }
         std::vector<float> c0(nC), c1(nC);
         if (hipStreamSynchronize(e->stream) || hipMemcpy(c0.data(), C0, nC * 4, hipMemcpyDeviceToHost) || hipMemcpy(c1.data(), C1, nC * 4, hipMemcpyDeviceToHost)) { set_err("gemm_mx_check: readback failed"); break; }
@@ -1985,8 +1938,6 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
             if (rows_gs) {
                 const size_t row = i / N, col = i % N, grp = col >> 5, e5 = col & 31;
                 v0 = half_at(c0.data(), (row * N + grp * 32) * 2 + e5) + half_at(c0.data(), (row * N + grp * 32) * 2 + 32 + e5);
-                if (gy) v1 = c1[i];
-                else
                 v1 = half_at(c1.data(), (row * N + grp * 32) * 2 + e5) + fp8_at(c1.data(), (row * N + grp * 32) * 4 + 64 + 16 * (e5 >> 3) + (e5 & 7)) * ldexp(1.0, -GLC_GX_SHIFT);
             } else if (units) {
                 const size_t u = i >> 3, j = i & 7;
@@ -1999,14 +1950,6 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
             sd += d * d; sr += v0 * v0;
         }
         out[0] = md; out[1] = mr; out[2] = sqrt(sd / nC); out[3] = sqrt(sr / nC); out[4] = 0;
-        if (special && gy) {
-            unsigned char ra[128], rw[128];
-            (void)hipMemcpy(ra, (const unsigned char*)Ay + 64, 48, hipMemcpyDeviceToHost); (void)hipMemcpy(rw, (const unsigned char*)Wy + 64, 48, hipMemcpyDeviceToHost);
-            fprintf(stderr, "  Ay row 0 fp6 area:"); for (int i = 0; i < 48; ++i) fprintf(stderr, " %02x", ra[i]);
-            fprintf(stderr, "\n  Wy row 0 fp6 area:"); for (int i = 0; i < 48; ++i) fprintf(stderr, " %02x", rw[i]);
-            (void)hipMemcpy(ra, (const unsigned char*)Ay + (size_t)(K / 32) * 112, 4, hipMemcpyDeviceToHost); (void)hipMemcpy(rw, (const unsigned char*)Wy + (size_t)(K / 32) * 112, 4, hipMemcpyDeviceToHost);
-            fprintf(stderr, "\n  scale bytes A %d %d %d %d  W %d %d %d %d\n", ra[0], ra[1], ra[2], ra[3], rw[0], rw[1], rw[2], rw[3]);
-        }
         if (special) fprintf(stderr, "[gemm_mx_check special] K = %d: split-f16 C[0] = %.6f, MX leg C[0] = %.6f C[1] = %.6f C[N+5] = %.6f; (case %d)\n", K, c0[0], c1[0], c1[1], c1[N + 5], spec);
         if (mode == 2) {
             std::vector<float2> p0((size_t)M * (N / 64)), p1(p0.size());
@@ -2019,7 +1962,6 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
     } while (0);
     (void)hipFree(A); (void)hipFree(W); (void)hipFree(A2); (void)hipFree(W2); (void)hipFree(C0); (void)hipFree(C1); (void)hipFree(R0); (void)hipFree(R1);
     (void)hipFree(bias); (void)hipFree(lnc); (void)hipFree(gam); (void)hipFree(bet); (void)hipFree(st); (void)hipFree(lp0); (void)hipFree(lp1);
-    (void)hipFree(Ay); (void)hipFree(Wy); (void)hipFree(Ry); (void)hipFree(Cy);
     return rc;
 }
 
@@ -2031,10 +1973,10 @@ float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, do
     if (!e || iters <= 0 || (e->dtype == GLC_F32 && !e->attn_split) || e->lastB <= 0 || e->cfg.backbone != GLC_BACKBONE_DEBERTA) {
         set_err("attn_bench: needs a DeBERTa engine (16-bit, or fp32 with split-f16 attention) and a previous forward"); return -1.f;
     }
+    constexpr int MX_DEV = 256 | 512 | 4096 | 16384 | 65536 | 131072 | 262144 | 1048576;     // the MX kernel's timing-only and measurement builds
+    if (variant & ~(255 | 1024 | 2048 | MX_DEV)) { set_err("attn_bench: no attention kernel takes these variant bits"); return -1.f; }
 #ifndef GLC_DEVELOPER
-    if (stamps || (variant & (256 | 512 | 4096 | 8192 | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152))) {
-        set_err("attn_bench: stamped builds, timing-only builds (wrong results) and the rejected attention kernels exist in developer builds only (make DEV=1)"); return -1.f;
-    }
+    if (stamps || (variant & MX_DEV)) { set_err("attn_bench: stamped and timing-only builds (wrong results) exist in developer builds only (make DEV=1)"); return -1.f; }
 #endif
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device), -1.f);
@@ -2048,13 +1990,9 @@ float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, do
     const bool mxk = (variant & 128) != 0;                    // bit 7: the MX-tile kernel (attention_mx.hip) on the MX tiles the last (MX) forward left; bits 8 / 9: its timing-only builds
     if (mxk) {
         if (!(sp && e->last_mx && e->mx_attn && w.PKm && w.PQm)) { set_err("attn_bench: the MX kernel needs a previous forward of the MX pipeline with MX attention"); return -1.f; }
-        a.PK = w.PKm; a.PQ = w.PQm; a.ctx_gs = 2; a.variant = variant & (256 | 512 | 1024 | 2048 | 4096 | 16384 | 65536 | 131072 | 262144 | 1048576 | 2097152);
-        a.idx16 = e->mx2tabs[Sp].first; a.tinfo = e->mx2tabs[Sp].second;
+        a.PK = w.PKm; a.PQ = w.PQm; a.ctx_gs = 2; a.variant = variant & (1024 | 2048 | MX_DEV);
     }
-    const bool mxk2 = mxk && (variant & 8192) != 0;           // bit 13: the bucket-space MX kernel (attention_mx2.hip)
-    if (mxk2 && !(a.idx16 && a.tinfo)) { set_err("attn_bench: no mx2 tables for this length"); return -1.f; }
-    const bool mxd = mxk && (variant & 524288) != 0;         // bit 19: two query tiles per wave, one wave per SIMD (csrc/dev/attention_mxd.hip; developer builds)
-    auto launch = [&]() -> const char* { return mxd ? glc_launch_attention_mxd(st, a) : mxk2 ? glc_launch_attention_mx2(st, a) : mxk ? glc_launch_attention_mx(st, a) : wg ? glc_launch_attention_wg(st, e->dtype, a) : glc_launch_attention(st, e->dtype, 2, a); };
+    auto launch = [&]() -> const char* { return mxk ? glc_launch_attention_mx(st, a) : wg ? glc_launch_attention_wg(st, e->dtype, a) : glc_launch_attention(st, e->dtype, 2, a); };
     for (int i = 0; i < 2; ++i) KCHK(launch(), -1.f);
     HIPCHK(hipEventRecord(e->t0, st), -1.f);
     for (int i = 0; i < iters; ++i) launch();
@@ -2103,7 +2041,7 @@ float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, do
         if (hipMalloc((void**)&dbuf, ns * sizeof(unsigned long long)) == hipSuccess) {
             (void)hipMemsetAsync(dbuf, 0, ns * sizeof(unsigned long long), st);
             AttnArgs as = a; as.stamps = dbuf;
-            const char* m = mxd ? glc_launch_attention_mxd(st, as) : mxk2 ? glc_launch_attention_mx2(st, as) : glc_launch_attention_mx(st, as);
+            const char* m = glc_launch_attention_mx(st, as);
             (void)hipStreamSynchronize(st);
             std::vector<unsigned long long> hs(ns);
             if (!m && hipMemcpy(hs.data(), dbuf, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -2112,15 +2050,6 @@ float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, do
                 const double nt = s[9] > 0 ? s[9] : 1;
                 double tot = 0;
                 for (int k = 0; k < 8; ++k) tot += s[k];
-                if (mxk2)
-                    fprintf(stderr, "[attn_mx2 stamps] per generic tile per wave (s_memtime ticks), %.0f tiles: K fragments + c2p store / gather + p2c / S issue %.0f | request wait + ring barrier %.0f | "
-                                    "DMA + row requests %.0f | image stores + gathers %.0f | softmax + P.V %.0f | c2p issue %.0f | total %.0f | s_memtime clock %.0f MHz\n",
-                            nt, (s[0] + s[1]) / nt, s[2] / nt, s[3] / nt, s[4] / nt, s[5] / nt, s[6] / nt, tot / nt, s[8] / (64 * 8) / 10.0);
-                else if (mxd)
-                    fprintf(stderr, "[attn_mxd stamps] per band step (two query tiles) per wave (s_memtime ticks), %.0f steps: DMA + row requests %.0f | gathers, bias, maxima %.0f | barrier X' %.0f | "
-                                    "M first half + softmax A %.0f | M second half + P.V A + softmax B %.0f | P.V B, c2p, ring stores %.0f | requests landed + barrier Y' %.0f | total %.0f\n",
-                            nt, s[0] / nt, s[1] / nt, s[2] / nt, s[3] / nt, s[4] / nt, s[5] / nt, s[6] / nt, tot / nt);
-                else
                 fprintf(stderr, "[attn_mx stamps] per band tile per wave (s_memtime ticks), %.0f tiles: request wait %.0f | K + c2p gather + p2c/S issue %.0f | row requests %.0f | "
                                 "barrier X %.0f | image stores + barrier Y %.0f | DMA + image gather %.0f | c2p issue + softmax + P.V %.0f | c2p store %.0f | total %.0f | s_memtime clock %.0f MHz\n",
                         nt, s[0] / nt, s[1] / nt, s[2] / nt, s[3] / nt, s[4] / nt, s[5] / nt, s[6] / nt, s[7] / nt, tot / nt, s[8] / (64 * 8) / 10.0);

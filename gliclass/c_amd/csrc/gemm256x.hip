@@ -727,27 +727,9 @@ bool glc_gemm256x_supported(const GemmArgs& a, int epi) {
     return epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESID || epi == EPI_SWIGLU;
 }
 
-// Developer builds (make DEV=1) keep the measured-and-rejected forms of this kernel in their own translation unit (csrc/dev/gemm256x_dev.hip:
-// GY images, the 16 x 16 MFMA shapes, stamped and timing-only builds); the product library has no path to them.
-#ifdef GLC_DEVELOPER
-const char* glc_launch_gemm256x_dev(hipStream_t st, int epi, const GemmArgs& a);
-#endif
-
 const char* glc_launch_gemm256x(hipStream_t st, int epi, const GemmArgs& a_in) {
     GemmArgs a = a_in;
-    if (a.gy || a.z16 || a.stamps || a.epi_abl || a.prio_mode >= 4) {
-#ifdef GLC_DEVELOPER
-        return glc_launch_gemm256x_dev(st, epi, a_in);
-#else
-        return "gemm256x: GY images, the 16 x 16 MFMA shapes, stamps and timing-only builds exist in developer builds only (make DEV=1)";
-#endif
-    }
-#ifdef GLC_DEVELOPER
-    {
-        static const bool z16_env = glc_dev_env("GLC_GEMM_Z16") && atoi(glc_dev_env("GLC_GEMM_Z16")) != 0;      // developer A/B: the 16 x 16 MFMA shapes
-        if (z16_env && a.K % 64 == 0) { a.z16 = 1; return glc_launch_gemm256x_dev(st, epi, a); }
-    }
-#endif
+    if (a.stamps || a.prio_mode >= 4) return "gemm256x: the MX GEMM has no stamped or timing-only build";
     if (!a.gx_sat) a.gx_sat = glc_gx_sat_ptr();              // fp8 range guard of the activation images this launch writes
     if (!a.act_sc) a.act_sc = glc_gx_act_sc();               // ... and the exponent of the activation rows (engine.hip act_sc)
     if (a.gx_rows <= 0) a.gx_rows = a.Mvalid > 0 ? a.Mvalid : a.Mpad;     // ... over the rows that exist (slack rows up to Mpad hold leftovers)

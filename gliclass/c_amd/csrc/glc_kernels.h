@@ -42,7 +42,7 @@ struct GemmArgs {
     int Mpad = 0, N = 0, K = 0;
     int Mvalid = 0, Sp = 0, nh = 0, H = 0;  // QKV only
     const void* W2 = nullptr; const float* bias2 = nullptr; int m_split = 0;   // gemm_nt (128-tile): rows >= m_split use W2 / bias2 (two-group GEMM)
-    unsigned long long* stamps = nullptr;   // gemm256s / gemm256x diagnostic builds only: per (block < 64, wave) cycle sums of the main-loop phases
+    unsigned long long* stamps = nullptr;   // gemm256s diagnostic builds only: per (block < 64, wave) cycle sums of the main-loop phases
     int qkv_skip_q = 0;                     // QKV: produce only K and V^T (pruned last layer)
     int w_presplit = 0;                     // gemm_nt split-f16 path (T = float): W already holds [32 hi halves | 32 lo halves] per 32-k group (glc_launch_presplit)
     int qkv_split = 0;                      // QKV, T = float: write Q / K / V^T units as [8 hi halves | 8 lo halves] (split-f16 attention, glc_common.h f16x8s)
@@ -72,15 +72,12 @@ struct GemmArgs {
     int qkv_mxt = 0;                        // gemm256x, EPI_QKV: write Q / K / V^T as MX tiles (glc_layout.h) for attention_mx.hip instead of split-f16 units
     int mx_ws = 0;                          // gemm256x: exponent of W's fp8 parts (GX rows written with glc_launch_to_gx(.., mx_ws))
     unsigned* gx_sat = nullptr;             // gemm256x: fp8 range guard counter (filled by the launcher from glc_gx_sat_ptr())
-    int z16 = 0;                            // gemm256x: the main loop on v_mfma_f32_16x16x32_f16 + v_mfma_scale_f32_16x16x128_f8f6f4 (same GX images; K % 64 == 0)
-    int gy = 0;                             // gemm256x: A, W, resid and C (where they are operand images) are GY rows — e2m3 parts with block scales (glc_common.h) — not GX rows
     int act_sc = 0;                         // gemm256x: exponent of the ACTIVATION GX rows it reads (A, resid) and writes (C); 0 unless the engine lowered it (engine.hip act_sc)
     int gx_rows = 0;                        // ... counted over rows [0, gx_rows) only: the slack rows up to Mpad hold leftovers of other forwards (0: Mvalid, else Mpad)
     // gemm256x, EPI_QKVR (decoder backbone, head_dim 128, nq and nkv even): N = (nq + 2 nkv) 128 fused projection columns; W rows (and bias)
     // of every Q / K head in the order glc_rope_perm128 gives (the two members of a rotate-half pair in one wave's accumulators); the
     // epilogue applies RoPE (rope_cs [Sp][64] (cos, sin)) and qscale (Q) in fp32 and writes Qh / Kh / Vt as the MX tiles of decoder_mx.hip.
     const float* rope_cs = nullptr; float qscale = 1.f; int nq = 0, nkv = 0;
-    int epi_abl = 0;                        // developer timing ablations of the GX-row epilogue (glc_debug_gemm_bench): 1 = no stores, 2 = every tile stores into rows [0, 256)
     int perm_cols = 0;                      // gemm256x, EPI_BIAS with gs_c_plain: columns [0, perm_cols) arrive in that order and are stored at their logical place
 };
 // EPI_QKVR: physical row p (0 .. 127) of a Q / K head of the fused projection weight holds logical feature glc_rope_perm128(p): the 32-blocks
@@ -135,20 +132,6 @@ const char* glc_launch_to_gx(hipStream_t st, void* w, size_t n, int sc, int word
 // the MX weight copies from the split-f16 (group-split) copies already on the device: largest magnitude (float bits, atomicMax into *d_bits), then the conversion
 const char* glc_launch_gs_absmax(hipStream_t st, const void* gs, size_t n, unsigned* d_bits);
 const char* glc_launch_gs_to_gx(hipStream_t st, const void* gs, void* gx, size_t n, int sc);
-// GY rows (glc_common.h: e2m3 parts with block scales, gy_row_bytes(K) per row): plain fp32 rows -> GY (A order / worder != 0: W order), the
-// projection weights from their split-f16 copies (W order), and back to fp32 (A order: x = hi + lo)
-#ifdef GLC_DEVELOPER      // GY rows (e2m3 cross terms with block scales: csrc/dev/gemm256x_dev.hip) — developer builds only
-const char* glc_launch_to_gy(hipStream_t st, const float* src, void* dst, size_t rows, int K, int worder);
-const char* glc_launch_gs_to_gy(hipStream_t st, const void* gs, void* dst, size_t rows, int K);
-#else
-inline const char* glc_launch_to_gy(hipStream_t, const float*, void*, size_t, int, int) { return "GY rows exist in developer builds only (make DEV=1)"; }
-inline const char* glc_launch_gs_to_gy(hipStream_t, const void*, void*, size_t, int) { return "GY rows exist in developer builds only (make DEV=1)"; }
-#endif
-#ifdef GLC_DEVELOPER
-const char* glc_launch_gy_to_f32(hipStream_t st, const void* src, float* dst, size_t rows, int K);
-#else
-inline const char* glc_launch_gy_to_f32(hipStream_t, const void*, float*, size_t, int) { return "GY rows exist in developer builds only (make DEV=1)"; }
-#endif
 #ifndef GLC_GX_SHIFT
 #define GLC_GX_SHIFT 11                     // GX rows: lo8 = e4m3((x - hi) * 2^(GLC_GX_SHIFT + sc)) (glc_common.h)
 #endif
@@ -197,7 +180,6 @@ struct AttnArgs {
     int ctx_gs = 0;                                   // workgroup-shared kernel, split operands: write CTX rows in the GS format (1) or the GX format (2)
     int ksplit = 0;                                   // per-wave band kernel with tile_flag: a workgroup with ONE flagged query tile splits that tile's keys over its 4 waves
     int prec = 0;                                     // workgroup-shared kernel, split units: (engine mask >> 8) & 63 — bits Q, K, V, P, PQ, PK rounded to f16
-    const void* idx16 = nullptr; const int4* tinfo = nullptr;   // attention_mx2.hip: the tables of glc_mx2_build_tables for this Sp
     unsigned* gx_sat = nullptr;                       // GX context rows: fp8 range guard counter (filled by the launchers from glc_gx_sat_ptr())
     int act_sc = 0;                                   // GX context rows: exponent of the activation images (engine.hip act_sc)
 };
@@ -210,22 +192,6 @@ const char* glc_launch_attention_wg(hipStream_t st, int dtype, const AttnArgs& a
 // Workgroup-shared band kernel on MX tiles (attention_mx.hip; the attention of the MX pipeline): Qh / Kh / Vt / PQ / PK are MX tiles
 // (glc_layout.h), CTX is written as GX rows; otab is the split-unit offset table.
 const char* glc_launch_attention_mx(hipStream_t st, const AttnArgs& a);
-// (Round 5's role-split kernel — a matrix wave and a softmax wave per SIMD, 1.32-1.36 ms against the band kernel's 1.12-1.17 — was deleted in round 6:
-//  docs/LOG_r05.md 3g, git history.)
-// Round 4: the same operands and outputs, position terms in bucket (delta) space, one independent wave per query tile (csrc/dev/attention_mx2.hip:
-// measured 4-6 % slower than the band kernel — a DEVELOPER kernel since round 5, not in the product library).
-// glc_mx2_build_tables: the kernel's two tables from the distance -> delta table of a padded length; false = this table does not have the
-// structure the kernel needs (the caller keeps glc_launch_attention_mx).
-#include <vector>
-#ifdef GLC_DEVELOPER
-const char* glc_launch_attention_mxd(hipStream_t st, const AttnArgs& a);      // csrc/dev/attention_mxd.hip: two query tiles per wave, one wave per SIMD (round 5)
-const char* glc_launch_attention_mx2(hipStream_t st, const AttnArgs& a);
-bool glc_mx2_build_tables(int Sp, int P, const int32_t* dtab, std::vector<unsigned char>& idx16, std::vector<int4>& tinfo);
-#else
-inline const char* glc_launch_attention_mxd(hipStream_t, const AttnArgs&) { return "attention(mxd): the two-tiles-per-wave kernel exists in developer builds only (make DEV=1)"; }
-inline const char* glc_launch_attention_mx2(hipStream_t, const AttnArgs&) { return "attention(mx2): the bucket-space kernel exists in developer builds only (make DEV=1)"; }
-inline bool glc_mx2_build_tables(int, int, const int32_t*, std::vector<unsigned char>&, std::vector<int4>&) { return false; }
-#endif
 // position tables at load: split-f16 units (Q / K layout, ntiles tiles of 32 rows x 64 columns) -> MX tiles; hl: (hi8 | lo8) order (PQ), else (lo8 | hi8) (PK)
 const char* glc_launch_units_to_mxt(hipStream_t st, const void* src, void* dst, int ntiles, int hl, unsigned* sat = nullptr, int planar = 0);   // sat: fp8 range guard counter (glc_common.h)
 

@@ -1,4 +1,4 @@
-"""Developer tool (GPU): the MX cross-term GEMM (gemm256x.hip) — numerics against the split-f16 GEMM, then timing and the stamped phase account."""
+"""Developer tool (GPU): the MX cross-term GEMM (gemm256x.hip) — numerics against the split-f16 GEMM, then timing."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -23,6 +23,4 @@ for rnd in range(2):
         for which in (6, 9):
             r[which] = e.L.glc_debug_gemm_bench(e.h, M_, N, K, EPI[ep], 10, which)
         print(f"r{rnd} {name:12s} split-f16 {r[6]*1e3:7.1f} us   MX {r[9]*1e3:7.1f} us  ({r[6]/r[9]:.3f}x)  {2.0*M_*N*K/r[9]/1e9:7.1f} TF fp32-equivalent", flush=True)
-for (M_, N, K) in ((65536, 3072, 768), (65536, 768, 3072)):
-    e.L.glc_debug_gemm_bench(e.h, M_, N, K, 0, 5, 10)
 e.close()

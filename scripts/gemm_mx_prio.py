@@ -1,4 +1,4 @@
-"""Developer tool (GPU): wave-priority policies of the MX GEMM main loop (gemm256x.hip), interleaved same-process rounds + stamps."""
+"""Developer tool (GPU): wave-priority policies of the MX GEMM main loop (gemm256x.hip), interleaved same-process rounds."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,6 +15,4 @@ for rnd in range(3):
         for pm in (0, 1, 2, 3):
             r[pm] = e.L.glc_debug_gemm_bench(e.h, M_, N, K, EPI[ep], 10, 100 * (1 + pm) + 9)
         print(f"r{rnd} {name:12s} " + "  ".join(f"prio{pm} {r[pm]*1e3:7.1f} us" for pm in r), flush=True)
-for pm in (0, 2, 3):
-    e.L.glc_debug_gemm_bench(e.h, 65536, 3072, 768, 0, 5, 100 * (1 + pm) + 10)
 e.close()

@@ -8,9 +8,8 @@ if len(sys.argv) > 1:
     from gliclass.c_amd.engine import Engine
     e = Engine(CONFIGS["tiny"], weights.make_weights(CONFIGS["tiny"], 1), dtype="f16")
     for (name, M, N, K, ep) in (("ffn2", 65536, 768, 3072, 2), ("ffn1", 65536, 3072, 768, 1)):
-        for which, tag in ((9, "GX"), (11, "GY")):
-            r = [e.L.glc_debug_gemm_bench(e.h, M, N, K, ep, 20, which) for _ in range(2)]
-            print(f"{sys.argv[1]:6s} {name} {tag}: {r[-1]*1e3:7.1f} us", flush=True)
+        r = [e.L.glc_debug_gemm_bench(e.h, M, N, K, ep, 20, 9) for _ in range(2)]
+        print(f"{sys.argv[1]:6s} {name}: {r[-1]*1e3:7.1f} us", flush=True)
     e.close()
 else:
     for d in ("random", "const", "zero"):

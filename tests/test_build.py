@@ -26,14 +26,14 @@ def test_product_library_ships_only_shipping_kernel_instantiations():
     ks = _kernel_names()
     assert ks, "no kernel names found in the library"
     text = "\n".join(ks)
-    # rejected experiments live in csrc/dev/ and are not linked
+    # rejected experiments (deleted; the git history keeps them) must not come back
     for gone in ("attn_mx2_kernel", "to_gy_kernel", "gy_to_f32_kernel"):
         assert gone not in text, gone
     # band kernel on MX tiles: <NW, ABL = 0, DIAG = false, RECOMP = true, FIXQ = true, XROT = true, DIET = true> only
     mx = [k for k in ks if "attn_mx_kernel<" in k]
     assert mx and all(re.search(r"attn_mx_kernel<[48], 0, false, true, true, true, true>", k) for k in mx), mx
-    # role-split kernel: <DIAG = false, XPRIO = 0> only
-    assert not [k for k in ks if "attn_mxs_kernel<" in k or "attn_mxd_kernel<" in k or "attn_mx2_kernel<" in k]      # rejected attention kernels: developer builds only
+    # rejected attention kernels (role-split, two tiles per wave, bucket space): deleted
+    assert not [k for k in ks if "attn_mxs_kernel<" in k or "attn_mxd_kernel<" in k or "attn_mx2_kernel<" in k]
     # MX GEMM: two template parameters (epilogue, transposed tile), nothing else
     gx = [k for k in ks if "gemm256x_kernel<" in k]
     assert gx and all(re.search(r"gemm256x_kernel<\d, (true|false)>\(", k) for k in gx), gx

@@ -69,45 +69,6 @@ def test_mx_pipeline_odd_batch_shapes():
         eng.close()
 
 
-def test_mx2_bucket_space_attention_vs_band_kernel_and_oracle():
-    """Round 4: the bucket-space MX attention (attention_mx2.hip: c2p / p2c in delta space, private to each wave; opt-in) on the shapes of the
-    test above — against the band kernel of the same engine (same products, other summation order on saturated tiles: accumulation noise)
-    and, one row each, against the CPU oracle.  Lengths beyond 512 exercise the log buckets and the saturated ends of the table,
-    S = 64 a single query tile, ragged rows the key-length cut.  A developer kernel since round 5 (csrc/dev/, make DEV=1): skipped on the product library."""
-    from gliclass.c_amd import _lib
-    if not _lib.hip().glc_debug_is_developer_build():
-        pytest.skip("attention_mx2 is compiled into developer builds only (make DEV=1)")
-    import oracle_c
-    from gliclass.c_amd import synth, weights
-    from gliclass.c_amd.config import CONFIGS
-    from gliclass.c_amd.engine import Engine
-    cfg = CONFIGS["base"]
-    eng = Engine.from_spec(cfg, "synthetic:base:42", dtype="f32")
-    w = None
-    sig = lambda x: 1.0 / (1.0 + np.exp(-x.astype(np.float64)))
-    try:
-        eng.set_length_buckets(1)
-        for (B, S, Cn, ragged) in ((64, 1024, 8, False), (100, 320, 8, True), (33, 1000, 5, True), (17, 2048, 8, True), (1024, 64, 1, False), (24, 704, 3, True)):
-            ids, mask, _ = synth.make_inputs(cfg, B, S, Cn, seed=B + S, ragged=ragged)
-            eng.set_mx2(False)
-            band = eng.forward(ids, mask)
-            assert eng.last_mx_attention(), (B, S)
-            eng.set_mx2(True)
-            got = eng.forward(ids, mask)
-            assert eng.last_mx_attention() and np.isfinite(got).all(), (B, S)
-            d = float(np.abs(sig(got) - sig(band)).max())
-            assert d <= 1e-4, (B, S, Cn, d)                       # measured <= 2e-5: only the saturated tiles are summed in another order
-            if S >= 1000:                                        # one whole row against the oracle (the log buckets and both saturated ends)
-                if w is None:
-                    w = weights.make_weights(cfg, 42)
-                b = B // 2
-                n = int(mask[b].sum())
-                ref = oracle_c.forward(cfg, w, ids[b:b + 1, :n], mask[b:b + 1, :n])
-                assert np.abs(sig(got[b:b + 1, :ref.shape[1]]) - sig(ref)).max() <= 5e-4, (B, S)
-    finally:
-        eng.close()
-
-
 def test_fp8_range_guard_device_resident_forward_contract():
     """a device-resident forward (glc_engine_forward_device) cannot be repeated behind the caller's back; its logits are
     valid only after glc_engine_sync() == 0 or glc_engine_device_forward_valid() == 1 (include/gliclass_hip.h).  With activation rows
@@ -178,10 +139,10 @@ def test_fp8_range_guard_device_resident_forward_contract():
         eng.close()
 
 
-def test_product_library_has_no_path_to_timing_only_or_stamped_kernels():
+def test_product_library_refuses_timing_only_stamped_and_deleted_kernels():
     """the product libgliclass_hip.so (plain `make`) contains no timing-only (wrong-result), stamped or rejected-experiment
-    kernel and no switch that reaches one: the attention microbenchmark refuses their variant bits and stamps, the MX GEMM refuses the GY /
-    16 x 16 / stamped / ablation requests.  (A developer build — make DEV=1 — has them all: skipped there.)"""
+    kernel and no switch that reaches one: the attention microbenchmark refuses their variant bits and stamps, the MX GEMM check refuses the
+    modes of deleted kernels.  (A developer build — make DEV=1 — has the timing-only and stamped builds: skipped there.)"""
     from gliclass.c_amd import _lib, synth
     from gliclass.c_amd.config import CONFIGS
     from gliclass.c_amd.engine import Engine
@@ -198,51 +159,19 @@ def test_product_library_has_no_path_to_timing_only_or_stamped_kernels():
         assert eng.last_mx_attention()
         cs = (C.c_double * 2)()
         assert L.glc_debug_attn_bench(eng.h, 1, 128, 0, cs) > 0                      # the shipping band kernel
-        for bits in (256, 512, 4096, 8192, 16384, 65536, 524288):                   # ablations, PV16, bucket-space kernel, spilled build, 16x16 timing build, two-tiles-per-wave kernel
+        for bits in (256, 512, 4096, 16384, 65536):                                  # ablations, PV16, spilled build, 16x16 timing build
             assert L.glc_debug_attn_bench(eng.h, 1, 128 | bits, 0, cs) < 0, bits
             assert b"developer builds only" in L.glc_last_error(), bits
+        for bits in (8192, 524288):                                                  # the deleted bucket-space and two-tiles-per-wave kernels
+            assert L.glc_debug_attn_bench(eng.h, 1, 128 | bits, 0, cs) < 0, bits
+            assert b"no attention kernel takes these variant bits" in L.glc_last_error(), bits
         assert L.glc_debug_attn_bench(eng.h, 1, 128, 1, cs) < 0                      # stamps
         out = (C.c_double * 8)()
-        for mode in (10, 20, 30):                                                    # GY images, 16 x 16 shapes, (deleted) 128 x 128 wave tile
+        for mode in (10, 20, 30):                                                    # (deleted) GY images, 16 x 16 shapes, 128 x 128 wave tile
             assert L.glc_debug_gemm_mx_check(eng.h, 512, 768, 768, 1.0, 0.02, mode, out) != 0, mode
-        with pytest.raises(RuntimeError, match="developer builds only"):            # no silent no-op either: the switches themselves refuse
-            eng.set_mx2(True)
-    finally:
-        eng.close()
-
-
-def test_mxd_two_tiles_per_wave_attention_vs_band_kernel():
-    """Round 5, developer kernel (csrc/dev/attention_mxd.hip: two query tiles per wave, one wave per SIMD, software-pipelined; make DEV=1 — skipped on
-    the product library): context rows against the band kernel on the SAME MX tiles of a forward, through the attention microbenchmark.  Same products
-    except the order in which the c2p band joins the scores and one shared product on saturated tiles: rows of magnitude ~5 must agree to two units of
-    the GX output format (2.5e-4; measured 1.2e-4).  Shapes: both saturated ends (S >= 1000), Sp % 256 != 0 (inactive waves), a single tile pair, ragged."""
-    from gliclass.c_amd import _lib, synth
-    from gliclass.c_amd.config import CONFIGS
-    from gliclass.c_amd.engine import Engine
-    L = _lib.hip()
-    if not L.glc_debug_is_developer_build():
-        pytest.skip("attention_mxd is compiled into developer builds only (make DEV=1)")
-    cfg = CONFIGS["base"]
-    eng = Engine.from_spec(cfg, "synthetic:base:42", dtype="f32")
-    try:
-        eng.set_length_buckets(1); eng.set_group_split(2)
-        for (B, S, ragged) in ((16, 1024, False), (5, 640, True), (3, 192, True), (2, 64, False), (2, 1536, True)):
-            ids, mask, _ = synth.make_inputs(cfg, B, S, 8, seed=3, ragged=ragged)
-            L.glc_debug_set_stop(eng.h, 1); eng.forward(ids, mask)
-            assert eng.last_mx_attention(), (B, S)
-            Sp = (S + 63) // 64 * 64
-            rows = B * Sp
-            out = {}
-            for v in (128, 128 | 524288):
-                cs = (C.c_double * 2)()
-                assert L.glc_debug_attn_bench(eng.h, 1, v, 0, cs) > 0, L.glc_last_error()
-                buf = np.zeros((rows, cfg.hidden), np.float32)
-                L.glc_debug_read_workspace(eng.h, 2, rows, buf.ctypes.data_as(C.c_void_p))
-                out[v] = buf.reshape(B, Sp, cfg.hidden)
-            valid = np.zeros((B, Sp), bool); valid[:, :S] = mask.astype(bool)
-            d = float(np.abs(out[128] - out[128 | 524288])[valid].max())
-            assert np.isfinite(out[128 | 524288][valid]).all() and d <= 2.5e-4, (B, S, d)
-        L.glc_debug_set_stop(eng.h, -1)
+        for which in (10, 11, 12, 13, 14, 1009):                                      # (deleted) stamped / GY / 16 x 16 / 128 x 128 MX GEMM legs, epilogue ablation
+            assert L.glc_debug_gemm_bench(eng.h, 512, 768, 768, 0, 1, which) < 0, which
+        assert not hasattr(L, "glc_debug_set_mx2")                                   # the bucket-space kernel's switch is gone with it
     finally:
         eng.close()
 
