@@ -1965,6 +1965,167 @@ int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, flo
     return rc;
 }
 
+}  // extern "C"
+namespace {
+// device buffers of one glc_debug_gemm_run call (freed when it returns)
+struct RunBufs {
+    std::vector<void*> v;
+    ~RunBufs() { for (void* p : v) (void)hipFree(p); }
+    void* get(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr; v.push_back(p); return p; }
+    void* up(const void* h, size_t bytes) { void* p = get(bytes); if (p && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return p; }
+};
+constexpr size_t RUN_GUARD = 1u << 20;      // bytes of guard before and after every output
+// bytes of output i (C, or Qh / Kh / Vt) the launch may write; 0 = that output does not exist (or the shape is one every launcher refuses)
+size_t gemm_run_out_bytes(const glc_gemm_run& r, int dtype, int i) {
+    const bool wide = r.kernel == GLC_GEMM_RUN_GS || r.kernel == GLC_GEMM_RUN_MX;       // GS / GX rows, split units, MX tiles and plain fp32: 4 bytes per element
+    const size_t es = wide ? 4 : esize(dtype);
+    if (r.epi == EPI_QKV || r.epi == EPI_QKVR) {
+        if (r.Sp <= 0 || r.Mvalid <= 0) return 0;
+        const size_t rows = (size_t)std::min(r.Mvalid, r.Mpad), B = (rows + r.Sp - 1) / r.Sp;
+        if (r.epi == EPI_QKVR) return r.nq > 0 && r.nkv > 0 ? B * (size_t)(i == 0 ? r.nq : r.nkv) * r.Sp * 128 * 4 : 0;
+        return r.nh > 0 ? B * (size_t)r.nh * r.Sp * 64 * es : 0;
+    }
+    if (i > 0) return 0;
+    const bool glu = r.epi == EPI_SWIGLU || r.epi == EPI_GEGLU;
+    return (size_t)r.Mpad * (size_t)(glu ? r.N / 2 : r.N) * es;
+}
+}  // namespace
+extern "C" {
+
+/* Kernel-level tests: one launcher call on caller-supplied operands, raw bytes back (include/gliclass_hip.h). */
+int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r) {
+    if (!e || !r || r->kernel < GLC_GEMM_RUN_128 || r->kernel > GLC_GEMM_RUN_AUTO || r->epi < EPI_BIAS || r->epi > EPI_GEGLU || r->Mpad <= 0 || r->N <= 0 || r->K <= 0 ||
+        r->Mpad > (1 << 20) || r->N > (1 << 20) || r->K > (1 << 20) || !r->A || !r->W || (r->W2 && r->kernel != GLC_GEMM_RUN_128) || r->ws_bytes > (1ull << 30)) {
+        set_err("gemm_run: bad args"); return -1;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHK(hipSetDevice(e->device), -1);
+    const int dtype = e->dtype, kern = r->kernel;
+    const bool gs = kern == GLC_GEMM_RUN_GS, mx = kern == GLC_GEMM_RUN_MX;
+    const size_t es = gs || mx ? 4 : esize(dtype);
+    auto up32 = [](size_t n) { return (n + 31) / 32 * 32; };      // the group converters take whole 32-groups (a row length they cut wrongly is one the launcher refuses)
+    const size_t nA = (size_t)r->Mpad * r->K, nW = (size_t)r->N * r->K, nC = (size_t)r->Mpad * r->N;
+    RunBufs bufs;
+    hipStream_t st = e->stream;
+    const char* msg = nullptr;
+    bool own = false;                               // msg is this entry's own failure (allocation, copy), not a refusal
+    // fp32 host values -> the operand image this kernel reads; role: 0 = activation rows (A, resid), 1 = weight rows
+    auto encode = [&](const float* h, size_t n, int role, bool plain) -> void* {
+        const size_t n32 = up32(n);
+        float* tmp = (float*)bufs.get(n32 * 4);
+        if (!tmp || hipMemsetAsync(tmp, 0, n32 * 4, st) != hipSuccess || hipMemcpyAsync(tmp, h, n * 4, hipMemcpyHostToDevice, st) != hipSuccess) { msg = "gemm_run: operand upload failed"; own = true; return nullptr; }
+        if (plain) return tmp;
+        if (gs) { msg = glc_launch_presplit(st, tmp, n32); return msg ? nullptr : tmp; }
+        if (mx) {
+            if (role == 1 && r->w_from_gs) {        // the engine's path: the split-f16 copy first, the GX copy from it
+                void* gx = bufs.get(n32 * 4);
+                if (!gx) { msg = "gemm_run: alloc failed"; own = true; return nullptr; }
+                msg = glc_launch_presplit(st, tmp, n32);
+                if (!msg) msg = glc_launch_gs_to_gx(st, tmp, gx, n32, r->mx_ws);
+                return msg ? nullptr : gx;
+            }
+            msg = glc_launch_to_gx(st, tmp, n32, role == 1 ? r->mx_ws : r->act_sc, role);
+            return msg ? nullptr : tmp;
+        }
+        if (dtype == GLC_F32) {
+            if (role == 1 && r->w_presplit) msg = glc_launch_presplit(st, tmp, n32);
+            return msg ? nullptr : tmp;
+        }
+        void* img = bufs.get(n32 * 2);
+        if (!img) { msg = "gemm_run: alloc failed"; own = true; return nullptr; }
+        msg = glc_launch_convert(st, dtype, tmp, img, n);
+        return msg ? nullptr : img;
+    };
+    auto fail = [&](const char* m, int rc) { (void)hipStreamSynchronize(st); set_err(m); return rc; };
+    GemmArgs g;
+    g.Mpad = r->Mpad; g.N = r->N; g.K = r->K; g.m_split = r->m_split; g.Mvalid = r->Mvalid; g.Sp = r->Sp; g.nh = r->nh; g.H = r->H; g.nq = r->nq; g.nkv = r->nkv;
+    g.qscale = r->qscale; g.qkv_skip_q = r->qkv_skip_q; g.qkv_split = r->qkv_split; g.qkv_mxt = r->qkv_mxt; g.gs_c_plain = r->gs_c_plain; g.gs_resid_plain = r->gs_resid_plain;
+    g.perm_cols = r->perm_cols; g.prec = r->prec; g.mx_ws = r->mx_ws; g.act_sc = r->act_sc; g.gx_rows = r->gx_rows;
+    g.w_presplit = kern == GLC_GEMM_RUN_128 && dtype == GLC_F32 && r->w_presplit;
+    g.A = encode(r->A, nA, 0, false);
+    if (!msg) g.W = encode(r->W, nW, 1, false);
+    if (!msg && r->W2) g.W2 = encode(r->W2, nW, 1, false);
+    if (!msg && r->resid) g.resid = encode(r->resid, nC, 0, gs && r->gs_resid_plain);
+    if (msg) return fail(msg, own ? -1 : -2);      // a converter's refusal counts as the launcher's: nothing has been launched
+    auto upf = [&](const float* h, size_t n) -> const float* { if (!h) return nullptr; const float* p = (const float*)bufs.up(h, n * 4); if (!p) msg = "gemm_run: upload failed"; return p; };
+    g.bias = upf(r->bias, r->N); g.bias2 = upf(r->bias2, r->N); g.ln_c = upf(r->ln_c, r->N); g.r_gamma = upf(r->r_gamma, r->N); g.r_beta = upf(r->r_beta, r->N);
+    g.a_stats = (const float2*)upf(r->a_stats, 2 * (size_t)r->Mpad); g.r_stats = (const float2*)upf(r->r_stats, 2 * (size_t)r->Mpad);
+    if (r->rope_cs) { if (r->Sp <= 0 || r->Sp > (1 << 16)) return fail("gemm_run: bad args", -1); g.rope_cs = upf(r->rope_cs, (size_t)r->Sp * 128); }
+    if (r->q_tile_flag) {
+        const size_t nf = (size_t)r->Mpad / 32 + 8;
+        unsigned char* f = (unsigned char*)bufs.get(nf);
+        if (!f || hipMemset(f, 0, nf) != hipSuccess || hipMemcpy(f, r->q_tile_flag, (size_t)r->Mpad / 32, hipMemcpyHostToDevice) != hipSuccess) msg = "gemm_run: upload failed";
+        g.q_tile_flag = f;
+    }
+    if (r->ws_bytes) { g.ws = (float*)bufs.get(r->ws_bytes); g.ws_bytes = r->ws_bytes; if (!g.ws) msg = "gemm_run: alloc failed"; }
+    if (msg) return fail(msg, -1);
+    // outputs: [guard | bytes | guard], all prefilled
+    struct Guarded { unsigned char* base = nullptr; size_t bytes = 0; };
+    Guarded outs[4];
+    const int fillb = r->fill & 255;
+    auto guarded = [&](Guarded& o, size_t bytes) {
+        o.bytes = bytes;
+        o.base = (unsigned char*)bufs.get(bytes + 2 * RUN_GUARD);
+        return o.base && hipMemsetAsync(o.base, fillb, bytes + 2 * RUN_GUARD, st) == hipSuccess;
+    };
+    for (int i = 0; i < 3; ++i) {
+        const size_t need = gemm_run_out_bytes(*r, dtype, i);
+        if (need > r->out_bytes[i]) return fail("gemm_run: out_bytes is smaller than the output this launch writes", -1);
+        if (!guarded(outs[i], std::max<size_t>(need, 16))) return fail("gemm_run: alloc failed", -1);
+    }
+    const size_t lp_bytes = (size_t)r->Mpad * (size_t)(r->N / 64) * 8;
+    if (r->want_ln_part) { if (!guarded(outs[3], std::max<size_t>(lp_bytes, 16))) return fail("gemm_run: alloc failed", -1); g.ln_part = (float2*)(outs[3].base + RUN_GUARD); }
+    if (r->epi == EPI_QKV || r->epi == EPI_QKVR) { g.Qh = outs[0].base + RUN_GUARD; g.Kh = outs[1].base + RUN_GUARD; g.Vt = outs[2].base + RUN_GUARD; }
+    else g.C = outs[0].base + RUN_GUARD;
+    unsigned* sat = (unsigned*)bufs.get(8);
+    if (!sat || hipMemsetAsync(sat, 0, 8, st) != hipSuccess) return fail("gemm_run: alloc failed", -1);
+    if (mx) g.gx_sat = sat;
+    // the one launcher call
+    switch (kern) {
+        case GLC_GEMM_RUN_128: msg = glc_launch_gemm(st, dtype, r->epi, g); break;
+        case GLC_GEMM_RUN_256S: msg = glc_launch_gemm256s(st, dtype, r->epi, g); break;
+        case GLC_GEMM_RUN_GS: msg = glc_launch_gemm256s_gs(st, r->epi, g); break;
+        case GLC_GEMM_RUN_MX: msg = glc_launch_gemm256x(st, r->epi, g); break;
+        default: msg = glc_launch_gemm_auto(st, dtype, r->epi, g); break;
+    }
+    if (msg) return fail(msg, -2);
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) { set_err(std::string("gemm_run: ") + hipGetErrorString(he)); return -1; }
+    auto back = [&](void* h, const void* d, size_t bytes) { return !h || !bytes || hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    bool ok = true;
+    for (int i = 0; i < 3; ++i) ok = ok && back(r->out[i], outs[i].base + RUN_GUARD, gemm_run_out_bytes(*r, dtype, i));
+    if (r->want_ln_part) ok = ok && back(r->ln_part, outs[3].base + RUN_GUARD, lp_bytes);
+    ok = ok && back(r->A_img, g.A, nA * es) && back(r->W_img, g.W, nW * es) && (!g.W2 || back(r->W2_img, g.W2, nW * es)) &&
+         (!g.resid || back(r->resid_img, g.resid, nC * (gs && r->gs_resid_plain ? 4 : es))) && back(r->sat, sat, 8);
+    std::vector<unsigned char> gd(RUN_GUARD);
+    r->guards_ok = 1;
+    r->cus = glc_device_cus();
+    for (int i = 0; i < 4 && ok; ++i) {
+        if (!outs[i].base) continue;
+        for (int side = 0; side < 2 && ok; ++side) {
+            ok = back(gd.data(), outs[i].base + (side ? RUN_GUARD + outs[i].bytes : 0), RUN_GUARD);
+            for (size_t k = 0; k < RUN_GUARD && ok; ++k) if (gd[k] != (unsigned char)fillb) { r->guards_ok = 0; break; }
+        }
+    }
+    if (!ok) { set_err("gemm_run: readback failed"); return -1; }
+    return 0;
+}
+
+int glc_debug_ln_stats_run(glc_engine* e, const float* part, int nparts, int M, float eps, int rms, float* stats) {
+    if (!e || !part || !stats || M <= 0 || nparts <= 0 || M > (1 << 20) || nparts > 1024) { set_err("ln_stats_run: bad args"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHK(hipSetDevice(e->device), -1);
+    RunBufs bufs;
+    const float2* dp = (const float2*)bufs.up(part, (size_t)M * nparts * 8);
+    float2* ds = (float2*)bufs.get((size_t)M * 8);
+    if (!dp || !ds) { set_err("ln_stats_run: alloc failed"); return -1; }
+    KCHK(glc_launch_ln_stats(e->stream, dp, nparts, ds, M, nparts * 64, eps, rms), -2);
+    HIPCHK(hipStreamSynchronize(e->stream), -1);
+    HIPCHK(hipMemcpy(stats, ds, (size_t)M * 8, hipMemcpyDeviceToHost), -1);
+    return 0;
+}
+
 /* Developer microbenchmark: re-run the band attention kernel `iters` times on the Q/K/V^T that the last forward left in the
  * workspace (layer-0 position tables), HIP-event timed.  checksum[0..1] = sum and sum of squares of the context output;
  * variant is passed through to the kernel; stamps != 0 adds one launch of the s_memtime-instrumented build and prints

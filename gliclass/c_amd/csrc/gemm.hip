@@ -323,6 +323,9 @@ template <typename T, bool SPLIT = false> void launch_t(hipStream_t st, int epi,
 //   Q/K/V^T outputs, glc_layout.h).
 const char* glc_launch_gemm(hipStream_t st, int dtype, int epi, const GemmArgs& a) {
     if (a.a_stats || a.r_stats || a.ln_part) return "gemm: the LayerNorm-fold arguments exist for the staggered 256-tile kernel only";
+    // (an epilogue this kernel has no build of used to fall through launch_t's switch: nothing launched and no error — or, with a split-K
+    //  workspace, the residual build on a null residual; tests/test_gpu_gemm_kernels.py test_refused_128_tile_unknown_epilogue)
+    if (epi != EPI_BIAS && epi != EPI_GELU && epi != EPI_RESID && epi != EPI_QKV) return "gemm: bad epilogue";
     const int esz = dtype == GLC_DT_F32 ? 4 : 2;
     if (a.Mpad <= 0 || a.Mpad % BM) return "gemm: Mpad must be a positive multiple of 128";
     if (a.N <= 0 || a.N % BN) return "gemm: N must be a multiple of 128";

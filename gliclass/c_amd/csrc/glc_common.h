@@ -199,8 +199,8 @@ __device__ __forceinline__ uint32_t glc_fp8x4(float a, float b, float c, float d
 }
 // fp8 range guard.  An activation beyond the e4m3 range (|x| 2^sc > 448) has no e4m3 image (the unclamped conversion of gx_split8 gives
 // 448 up to 464 and NaN beyond; a clamped one would silently leave that element at single-f16 accuracy).  Synthetic weights never get there; the outlier channels of trained checkpoints (10^2 .. 10^4 in the raw residual
-// stream of a pre-norm decoder) do.  Every producer of an activation operand image (GX rows, MX tiles) therefore counts such elements
-// in a per-engine device counter (sat != nullptr); the engine reads it with the logits and repeats a forward that counted any on the
+// stream of a pre-norm decoder) do.  Every producer of an activation operand image (GX rows, MX tiles) therefore counts the 8-element store
+// units that hold such an element in a per-engine device counter (sat != nullptr); the engine reads it with the logits and repeats a forward that counted any on the
 // split-f16 kernels, whose operands hold up to 65504 (engine.hip forward_one).
 __device__ __forceinline__ void gx_range_note(const float (&v)[8], float k_hi, unsigned* sat) {
     if (!sat) return;

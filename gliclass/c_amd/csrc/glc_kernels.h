@@ -136,6 +136,8 @@ const char* glc_launch_gs_to_gx(hipStream_t st, const void* gs, void* gx, size_t
 #define GLC_GX_SHIFT 11                     // GX rows: lo8 = e4m3((x - hi) * 2^(GLC_GX_SHIFT + sc)) (glc_common.h)
 #endif
 // fp8 exponent for a weight tensor whose largest magnitude is maxabs: 2^sc maxabs <= 240 (e4m3 saturates at 448)
+// (the lower clamp, -30, answers maxabs >= 240 * 2^30, far beyond the f16 range of the hi halves (65504): no GX image of such weights exists.  For
+//  weights the format can hold the exponent is >= -9; a launch at mx_ws = -30 is accepted, and every fp8 part of representable weights is then zero)
 inline int glc_gx_weight_exponent(float maxabs) {
     if (!(maxabs > 0.f)) return 0;
     int sc = (int)floorf(log2f(240.0f / maxabs));

@@ -213,6 +213,43 @@ void glc_delta_table(int S, int bucket_size, int max_position, int32_t* out);
 float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iters, int which);
 /* Developer check: MX cross-term GEMM against the split-f16 GEMM on the same random operands (engine.hip). */
 int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, float w_amp, int mode, double* out);
+/* Kernel-level tests (tests/test_gpu_gemm_kernels.py): ONE launcher call of one GEMM kernel on operands the caller chose.
+ * The host fp32 operands are encoded with the library's own converters (glc_launch_convert / _presplit / _to_gx / _gs_to_gx), the launcher
+ * runs once, and the RAW BYTES of every output, of ln_part, of the encoded operand images and the two words of the fp8 range counter come
+ * back; decoding them is the caller's business (tests/gemm_ref.py: a second reading of the formats).  Every output sits between two guard
+ * regions and is, like them, prefilled with the byte `fill`.  A shape the launcher (or, before it, one of the converters) refuses returns -2
+ * with its message in glc_last_error() and no GEMM launched; -1 = bad arguments or a HIP error. */
+enum { GLC_GEMM_RUN_128 = 0,     /* gemm.hip, the engine's dtype (fp32 engines: the split-f16 path; w_presplit = W split at load) */
+       GLC_GEMM_RUN_256S = 1,    /* gemm256s.hip, 16-bit engines */
+       GLC_GEMM_RUN_GS = 2,      /* gemm256s.hip on group-split rows */
+       GLC_GEMM_RUN_MX = 3,      /* gemm256x.hip on GX rows */
+       GLC_GEMM_RUN_AUTO = 4 };  /* glc_launch_gemm_auto, the engine's dtype */
+typedef struct glc_gemm_run {
+    /* ---- in ---- */
+    int32_t kernel, epi;                               /* GLC_GEMM_RUN_*; EPI_* of csrc/glc_kernels.h (0 bias, 1 GELU, 2 residual, 3 QKV, 4 SwiGLU, 5 QKVR, 6 GeGLU) */
+    int32_t Mpad, N, K;
+    const float *A, *W, *bias, *W2, *bias2, *resid;    /* host fp32: A [Mpad,K], W / W2 [N,K], bias / bias2 [N], resid [Mpad,N]; null = absent */
+    const float *a_stats, *ln_c, *r_stats, *r_gamma, *r_beta, *rope_cs;   /* a_stats / r_stats [Mpad] (x, y) pairs; ln_c, r_gamma, r_beta [N]; rope_cs [Sp][64] (cos, sin) */
+    const unsigned char* q_tile_flag;                  /* [Mpad / 32] */
+    int32_t m_split, Mvalid, Sp, nh, H, nq, nkv;
+    float qscale;
+    int32_t qkv_skip_q, qkv_split, qkv_mxt, gs_c_plain, gs_resid_plain, perm_cols, prec, mx_ws, act_sc, gx_rows;
+    int32_t w_presplit;                                /* GLC_GEMM_RUN_128 on an fp32 engine: W (and W2) through glc_launch_presplit, as the engine loads them */
+    int32_t w_from_gs;                                 /* GLC_GEMM_RUN_MX: W through glc_launch_presplit + glc_launch_gs_to_gx (the engine's path) instead of glc_launch_to_gx */
+    int32_t want_ln_part;                              /* pass an ln_part buffer [Mpad][N / 64] (x, y) */
+    int32_t fill;                                      /* byte the outputs, ln_part and the guards are prefilled with */
+    uint64_t ws_bytes;                                 /* split-K workspace of the 128-tile kernel; 0 = none */
+    /* ---- out (host buffers of the caller; a null pointer skips that copy) ---- */
+    void* out[3]; uint64_t out_bytes[3];               /* C, or Qh / Kh / Vt: capacity, at least the bytes of that output (engine.hip gemm_run_out_bytes) */
+    void* ln_part;                                     /* Mpad * (N / 64) * 8 bytes */
+    void *A_img, *W_img, *W2_img, *resid_img;          /* the encoded operands: element bytes (2, or 4 for fp32 / GS / GX) x count */
+    uint32_t sat[2];                                   /* the fp8 range counter after the launch */
+    int32_t guards_ok;                                 /* 1: every guard region still holds `fill` */
+    int32_t cus;                                       /* compute units of the engine's device: what the split-K part count and the small-M rule of the launchers depend on */
+} glc_gemm_run;
+int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r);
+/* glc_launch_ln_stats on host partials part [M][nparts] (sum, M2) -> stats [M] (mean, rstd) pairs; rms: (0, 1 / sqrt(E[x^2] + eps)) */
+int glc_debug_ln_stats_run(glc_engine* e, const float* part, int nparts, int M, float eps, int rms, float* stats);
 /* Developer microbenchmark of the band attention kernel on the workspace of the last forward (see engine.hip). */
 float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, double* checksum);
 int glc_debug_is_developer_build(void);                  /* 1: built with make DEV=1 (developer kernels, stamps, GLC_* switches); 0: the product library */
