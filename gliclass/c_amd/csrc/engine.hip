@@ -1,152 +1,23 @@
 // Engine = what g_ort->CreateSession + g_ort->Run are to /root/reference/src/model.c:173,269:
 // weight residency in HBM, workspace management, and the per-forward launch sequence on ONE HIP
 // stream.  Implements include/gliclass_hip.h.  No CPU fallback exists: without a GPU every entry
-// point fails loudly through glc_last_error().
-#include <hip/hip_runtime.h>
-
+// point fails loudly through glc_last_error().  The developer entries that allocate buffers of their
+// own or launch kernels outside a forward (microbenchmarks, glc_debug_gemm_run, workspace read-back)
+// are in engine_debug.hip.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <map>
-#include <mutex>
 #include <algorithm>
-#include <string>
-#include <vector>
 
-#include "../../../include/gliclass_hip.h"
-#include "glc_kernels.h"
+#include "engine_internal.h"
 #include "glc_layout.h"
 
 namespace {
-
 thread_local std::string g_err;
-void set_err(const std::string& s) { g_err = s; }
-
-#define HIPCHK(expr, ret)                                                                          \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            set_err(std::string(#expr) + ": " + hipGetErrorString(_e));                            \
-            return ret;                                                                            \
-        }                                                                                          \
-    } while (0)
-#define KCHK(expr, ret)                                                                            \
-    do {                                                                                           \
-        const char* _m = (expr);                                                                   \
-        if (_m) { set_err(_m); return ret; }                                                       \
-    } while (0)
-
-inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-inline size_t esize(int dtype) { return dtype == GLC_F32 ? 4 : 2; }
-
-enum { PC_SCAN = 0, PC_EMBED, PC_QKV, PC_ATTN, PC_ATTN_OUT, PC_LN, PC_FFN1, PC_FFN2, PC_HEAD, PC_LAST, PC_N };
-const char* const kProfNames[PC_N] = {"scan_rows", "embed_ln", "gemm_qkv", "attention", "gemm_attn_out", "layernorm",
-                                      "gemm_ffn1_gelu", "gemm_ffn2", "head", "last_layer_pruned"};
-
-struct DecLayerW {                     // decoder-style backbone (decoder.hip)
-    void *Wqkv = nullptr, *Wo = nullptr, *Wgu = nullptr, *Wd = nullptr;       // T: [(nq+2nkv)d, H], [H, nq d], [2I, H] (gate rows | up rows), [H, I]
-    float *bqkv = nullptr, *ln1 = nullptr, *ln2 = nullptr;                    // f32
-    void *Wqkvf = nullptr, *Wguf = nullptr;                                   // fp32 mode, RMSNorm folded into the GEMMs: Wqkv diag(ln1), Wgu diag(ln2), group-split
-    void *Wqkvf_x = nullptr, *Wo_x = nullptr, *Wguf_x = nullptr, *Wd_x = nullptr;   // MX pipeline: the same four as GX rows + their fp8 exponents
-    int ws_qkvf = 0, ws_o = 0, ws_guf = 0, ws_d = 0;
-    float* bqkv_p = nullptr;            // bqkv in the row order of a Wqkvf_x built for the RoPE epilogue (glc_rope_perm128), else null
-};
-
-struct LayerW {
-    void *Wqkv = nullptr, *Wo = nullptr, *W1 = nullptr, *W2 = nullptr;       // T
-    float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;       // f32
-    float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr; // f32
-    void *PK = nullptr, *PQ = nullptr;                                        // T [nh, P, 64]
-    void *PKs = nullptr, *PQs = nullptr;                                      // fp32 mode: the same tables as split-f16 units (band kernel, AttnArgs::split)
-    // LayerNorm folded into the group-split GEMMs (GemmArgs::a_stats): W1 . diag(ln1 gamma), Wqkv . diag(previous layer's ln2 gamma)
-    // as group-split rows, their row sums c and the folded biases d = W beta + b
-    void *W1f = nullptr, *Wqkvf = nullptr;
-    float *c1 = nullptr, *d1 = nullptr, *cq = nullptr, *dq = nullptr;
-    // MX pipeline (glc_engine::mx): the projection weights once more as GX rows (glc_common.h) with their fp8 exponents
-    void *PKm = nullptr, *PQm = nullptr;                                     // the position tables as MX tiles (attention_mx.hip)
-    void *Wqkv_x = nullptr, *Wqkvf_x = nullptr, *Wo_x = nullptr, *W1f_x = nullptr, *W2_x = nullptr;
-    int ws_qkv = 0, ws_qkvf = 0, ws_o = 0, ws_1f = 0, ws_2 = 0;
-};
-
-}  // namespace
-
-struct glc_engine {
-    glc_model_config cfg{};
-    int dtype = GLC_F32, device = 0, attn_impl = 0;
-    bool prune_last = true;         // last layer only on the rows the head reads (exact)
-    bool w_presplit = false;        // weights of the split-f16 fp32 GEMMs are split once at load (encoder layers in fp32 mode; head projectors in every mode)
-    bool dec_split = false;         // decoder backbone, fp32 mode: RoPE/layout pass writes split-f16 units, grouped-query attention on three-MFMA products
-    bool attn_split = false;        // fp32 mode: band attention on split-f16 operands (three f16 MFMAs per product); GLICLASS_F32_ATTN=native turns it off
-    bool mx_built = false, mx = false;   // MX cross-term projections (gemm256x.hip) on GX rows: allowed for this engine / pipeline selected (GLICLASS_MX, glc_debug_set_mx)
-    bool mx_ready = false;               // ... and the GX copies of the projection weights exist: built from the split-f16 copies by the first forward that takes the pipeline
-    size_t mx_bytes = 0;                 // their size (glc_debug_mx_weight_bytes)
-    bool last_mx = false;                // the last forward ran the MX pipeline
-    bool last_mx_attn = false;           // ... and its attention ran on MX tiles (attention_mx.hip)
-    bool dec_rope_epi = true;            // decoder MX pipeline: RoPE + MX tiles as the QKV projection's epilogue (gemm256x EPI_QKVR); GLC_DEC_ROPE_EPI=0: the separate pass
-    bool mx_attn = true;                 // MX pipeline: attention on MX tiles (attention_mx.hip); false: split-f16 units (GLC_MX_ATTN=0, glc_debug_set_mx_attention)
-    int debug_stop = -1;                 // developer: leave run_forward after stage (10 * layer + k), k = 0 QKV, 1 attention, 2 attn-out, 3 FFN1, 4 FFN2 (+ LayerNorm): workspace inspection
-    int prec_mask = 0;              // precision-budget switches (PM_* of glc_kernels.h; glc_debug_set_precision_mask): operands rounded to f16 in the group-split pipeline
-    int gs_mode = 1;                // fp32 mode, group-split activations + 256-tile LDS-DMA GEMMs: 0 off, 1 auto (large shapes), 2 whenever the shapes allow (tests)
-    bool last_gs = false;           // the last forward ran the group-split pipeline
-    bool ln_fused = true;           // group-split pipeline: LayerNorm folded into the GEMMs around it (GLC_LNF=0: separate LayerNorm kernels)
-    bool last_lnf = false;          // the last forward ran with LayerNorm / RMSNorm folded into its GEMMs
-    float2 *statsA = nullptr, *statsB = nullptr, *ln_part = nullptr;     // (mean, rstd) per row of X / H1 when they hold raw sums; the producers' partials
-    int max_buckets = 4;            // host-buffer forward: split a ragged batch into <= this many length groups (1 = off)
-    int last_groups = 1;            // groups the last host-buffer forward ran as
-    int range_retries = 0;          // host-buffer forwards repeated with the norms unfused because the folded one came out non-finite
-    // fp8 range guard of the MX pipeline (glc_common.h gx_range_note): device counter of activation elements beyond the e4m3 range, its value after the
-    // last checked forward, a pinned host slot for the device-resident path; forwards repeated on the split-f16 kernels because they counted
-    // any; consecutive such forwards (the model has outlier channels: after kFp8Sticky of them the engine leaves the MX pipeline for good)
-    unsigned* d_gxsat = nullptr; unsigned gxsat_seen[2] = {0, 0}; unsigned* h_gxsat = nullptr;      // two words: [0] activation rows (GX images, exponent act_sc), [1] Q / K / V MX tiles (exponent 0)
-    int fp8_retries = 0, fp8_streak = 0; bool fp8_sticky_off = false, fp8_device_pending = false;
-    int device_invalid = 0;                    // a device-resident forward since the last glc_engine_sync left the fp8 range (1: rows only, 2: tiles): its logits are not valid
-    // Activation exponent of the MX pipeline's GX rows (hi8 = e4m3(x 2^act_sc), glc_common.h): 0 until a forward leaves the e4m3 range (|x| > 448);
-    // the guard's FIRST answer is then kActScLow = -5 for this engine (rows hold |x| up to 14336, elements below 0.5 keep fewer hi8 bits — their
-    // cross terms are 2^-16 of a unit product either way) and the forward is repeated on the MX pipeline; only what still leaves the range
-    // (or an MX tile of the attention: Q, K, V, P keep exponent 0) goes to the split-f16 kernels.
-    int act_sc = 0;
-    float* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;     // fp32 partial tiles of the split-K GEMM path (small M)
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-    std::vector<void*> allocs;      // everything freed at destroy
-    // weights
-    void* emb = nullptr; float *eln_g = nullptr, *eln_b = nullptr;
-    std::vector<LayerW> layers;
-    std::vector<DecLayerW> dlayers; float* final_norm = nullptr;      // decoder backbone; ModernBERT: Wgu = Wi, Wd = mlp.Wo, ln1 / ln2 = attn_norm / mlp_norm
-    float* zero_bias = nullptr;                                       // ModernBERT: [H] zeros, the beta of its bias-free LayerNorms
-    std::map<std::pair<int, float>, float*> ropes;                    // (Sp, theta) -> [Sp][d/2][cos,sin]
-    void *QKV = nullptr, *GU = nullptr, *X2 = nullptr;                // decoder workspace: fused QKV rows, [gate|up] rows, second residual buffer
-    bool fused_swiglu = false;                                        // Wgu rows interleaved 16 gate / 16 up: SwiGLU runs in the GEMM epilogue
-    float* headw[8] = {nullptr};
-    float* scw[8] = {nullptr};           // the scorer's own tensors (weighted-dot: 8, mlp: 6, simple: none), fp32
-    float* scorer_ws = nullptr;          // its row buffers
-    int P = 0;
-    // workspace
-    int capM = 0, capB = 0, capIds = 0, capC = 0, capHeadRows = 0, capSel = 0, capGU = 0;
-    void *Xs = nullptr, *Qs = nullptr, *CTXs = nullptr, *T1s = nullptr, *H1s = nullptr, *FFs = nullptr;   // compact rows of the pruned last layer
-    int *sel_b = nullptr, *sel_q = nullptr;
-    unsigned char* tile_flag = nullptr; size_t capFlag = 0;
-    void *X = nullptr, *Qh = nullptr, *Kh = nullptr, *Vt = nullptr, *CTX = nullptr, *T1 = nullptr, *H1 = nullptr, *FF = nullptr;
-    float* kbias = nullptr; int *klen = nullptr, *kfirst = nullptr, *cls_pos = nullptr, *cls_cnt = nullptr;
-    int64_t *d_ids = nullptr, *d_mask = nullptr;
-    float *Gt = nullptr, *G1t = nullptr, *G2t = nullptr, *d_logits = nullptr;   // head rows: [text | class] groups, 128-aligned
-    std::map<int, int32_t*> dtabs;
-    std::map<int, int2*> mtabs;                // Sp -> the MX band kernel's ready-made row offsets (round 6; fp32 mode only): glc_kernels.h AttnArgs::mtab
-    std::map<int, int2*> otabs;                // Sp -> byte offsets of the PQ / PK rows per relative distance (band kernel, 16-bit)
-    std::map<int, std::pair<int, int>> dsat;   // Sp -> (rsat_pos, rsat_neg)
-    // last forward
-    int lastB = 0, lastS = 0, lastSp = 0;
-    // debug
-    bool keep_hidden = false; void* hidden_dump = nullptr; size_t hidden_cap = 0;
-    // timing / profile
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    bool profile = false;
-    struct Ev { hipEvent_t a, b; int cls; };
-    std::vector<Ev> evs; size_t ev_used = 0;
-    float prof_ms[PC_N] = {0}; int prof_n[PC_N] = {0};
-};
+}
+void glc_set_err(const std::string& s) { g_err = s; }
 
 namespace {
 
@@ -160,8 +31,8 @@ struct GxScope {
 void* dmalloc(glc_engine* e, size_t bytes, bool zero = true) {
     void* p = nullptr;
     if (bytes == 0) bytes = 16;
-    if (hipMalloc(&p, bytes) != hipSuccess) { set_err("hipMalloc failed for " + std::to_string(bytes) + " bytes"); return nullptr; }
-    if (zero && hipMemsetAsync(p, 0, bytes, e->stream) != hipSuccess) { set_err("hipMemset failed"); return nullptr; }
+    if (hipMalloc(&p, bytes) != hipSuccess) { glc_set_err("hipMalloc failed for " + std::to_string(bytes) + " bytes"); return nullptr; }
+    if (zero && hipMemsetAsync(p, 0, bytes, e->stream) != hipSuccess) { glc_set_err("hipMemset failed"); return nullptr; }
     e->allocs.push_back(p);
     return p;
 }
@@ -200,14 +71,14 @@ void prof_collect(glc_engine* e) {
 float* upload_f32(glc_engine* e, const float* src, size_t n) {
     float* d = (float*)dmalloc(e, n * sizeof(float), false);
     if (!d) return nullptr;
-    if (hipMemcpyAsync(d, src, n * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) { set_err("H2D failed"); return nullptr; }
+    if (hipMemcpyAsync(d, src, n * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) { glc_set_err("H2D failed"); return nullptr; }
     return d;
 }
 // host f32 -> device T at dst (dst preallocated), via a temporary f32 staging buffer
 bool upload_as(glc_engine* e, const float* src, size_t n, void* dst, float* staging) {
-    if (hipMemcpyAsync(staging, src, n * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) { set_err("H2D failed"); return false; }
+    if (hipMemcpyAsync(staging, src, n * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) { glc_set_err("H2D failed"); return false; }
     const char* m = glc_launch_convert(e->stream, e->dtype, staging, dst, n);
-    if (m) { set_err(m); return false; }
+    if (m) { glc_set_err(m); return false; }
     return hipStreamSynchronize(e->stream) == hipSuccess;   // staging is reused by the caller
 }
 
@@ -215,8 +86,8 @@ constexpr int kFp8Sticky = 2;
 bool init_range_guard(glc_engine* e) {
     if (e->d_gxsat) return true;
     e->d_gxsat = (unsigned*)dmalloc(e, 2 * sizeof(unsigned), false);
-    if (!e->d_gxsat || hipMemset(e->d_gxsat, 0, 2 * sizeof(unsigned)) != hipSuccess) { set_err("range-guard counter alloc failed"); return false; }
-    if (hipHostMalloc((void**)&e->h_gxsat, 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) { e->h_gxsat = nullptr; set_err("range-guard host slot alloc failed"); return false; }
+    if (!e->d_gxsat || hipMemset(e->d_gxsat, 0, 2 * sizeof(unsigned)) != hipSuccess) { glc_set_err("range-guard counter alloc failed"); return false; }
+    if (hipHostMalloc((void**)&e->h_gxsat, 2 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) { e->h_gxsat = nullptr; glc_set_err("range-guard host slot alloc failed"); return false; }
     e->h_gxsat[0] = e->h_gxsat[1] = 0;
     return true;
 }
@@ -230,7 +101,7 @@ template <class T> bool regrow(glc_engine* e, T*& p, size_t bytes) {
 template <class T> T* upload_table(glc_engine* e, const std::vector<T>& t, const char* what) {
     T* d = (T*)dmalloc(e, t.size() * sizeof(T), false);
     if (!d) return nullptr;
-    if (hipMemcpy(d, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { set_err(std::string(what) + " upload failed"); return nullptr; }
+    if (hipMemcpy(d, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { glc_set_err(std::string(what) + " upload failed"); return nullptr; }
     return d;
 }
 
@@ -393,7 +264,7 @@ bool upload_scorer(glc_engine* e, const float* const* t) {
     for (int i = 0; i < cnt; ++i) {
         e->scw[i] = upload_f32(e, t[i], n[i]);
         if (!e->scw[i]) return false;
-        if (mat[i] && e->w_presplit) { const char* pm = glc_launch_presplit(e->stream, e->scw[i], n[i]); if (pm) { set_err(pm); return false; } }
+        if (mat[i] && e->w_presplit) { const char* pm = glc_launch_presplit(e->stream, e->scw[i], n[i]); if (pm) { glc_set_err(pm); return false; } }
     }
     return true;
 }
@@ -418,9 +289,9 @@ const char* launch_gemm128(glc_engine* e, int dt, int epi, GemmArgs a) {
 // (the body; `made` collects every pointer slot it fills so that build_mx_weights can undo a partial build)
 static bool build_mx_weights_impl(glc_engine* e, std::vector<void**>& made) {
     unsigned* d_bits = (unsigned*)e->splitk_ws;          // (scratch: the split-K workspace is idle between launches)
-    if (!d_bits) { set_err("MX weights: no scratch"); return false; }
+    if (!d_bits) { glc_set_err("MX weights: no scratch"); return false; }
     auto copy = [&](const void* gs, size_t n, void*& dst, int& ws) -> bool {
-        if (!gs) { set_err("MX weights: a split-f16 source copy is missing"); return false; }
+        if (!gs) { glc_set_err("MX weights: a split-f16 source copy is missing"); return false; }
         unsigned bits = 0;
         HIPCHK(hipMemsetAsync(d_bits, 0, sizeof(unsigned), e->stream), false);
         KCHK(glc_launch_gs_absmax(e->stream, gs, n, d_bits), false);
@@ -1025,7 +896,7 @@ bool upload_head(glc_engine* e, const float* const* ht) {
         if (i % 2 == 0 && e->w_presplit) KCHK(glc_launch_presplit(e->stream, e->headw[i], H * H), false);
     }
     if (!upload_scorer(e, ht + GLC_TENSORS_HEAD)) return false;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); return false; }
+    if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); return false; }
     return true;
 }
 
@@ -1061,7 +932,7 @@ bool create_decoder(glc_engine* e, const float* const* tensors, float* staging) 
         w.bqkv = upload_f32(e, bqkv.data(), NQKV);
         w.ln1 = upload_f32(e, t[0], H); w.ln2 = upload_f32(e, t[8], H);
         if (!w.bqkv || !w.ln1 || !w.ln2) return false;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // bqkv host buffer is reused
+        if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err("sync failed"); return false; }   // bqkv host buffer is reused
     }
     e->final_norm = upload_f32(e, tensors[1 + GLC_DEC_TENSORS_PER_LAYER * L], H);
     return e->final_norm != nullptr;
@@ -1148,7 +1019,7 @@ bool create_deberta(glc_engine* e, const float* const* tensors, float* staging) 
             ln_bound = fmaxf(ln_bound, fmaxf(fabsf(t[8][i]) * sqrtf((float)H) + fabsf(t[9][i]), fabsf(t[14][i]) * sqrtf((float)H) + fabsf(t[15][i])));
         }
         if (!w.bqkv || !w.bo || !w.ln1g || !w.ln1b || !w.b1 || !w.b2 || !w.ln2g || !w.ln2b) return false;
-        if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // bqkv host buffer is reused
+        if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err("sync failed"); return false; }   // bqkv host buffer is reused
         // position projections (HF:296-302, share_att_key): PQ = query_proj(R)*log2e/sqrt(3d), PK = key_proj(R)
         GemmArgs g;
         g.A = Rt; g.W = w.Wqkv; g.bias = w.bqkv; g.Qh = w.PQ; g.Kh = w.PK; g.Vt = vscratch;
@@ -1193,7 +1064,7 @@ bool create_deberta(glc_engine* e, const float* const* tensors, float* staging) 
                 w.cq = upload_f32(e, cv.data(), 3 * (size_t)H); w.dq = upload_f32(e, dv.data(), 3 * (size_t)H);
                 if (!w.cq || !w.dq) return false;
             }
-            if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // host vectors are reused
+            if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err("sync failed"); return false; }   // host vectors are reused
         }
         if (e->mx_built && w.PKs && w.PQs) {
             // MX pipeline: the GX copies of the projection weights are built by the first forward that takes the pipeline (build_mx_weights);
@@ -1222,14 +1093,14 @@ bool create_deberta(glc_engine* e, const float* const* tensors, float* staging) 
         fprintf(stderr, "gliclass: LayerNorm gains of this checkpoint allow activations up to %.0f (beyond the fp8 range of the MX operand images, 448); "
                         "this engine's activation rows carry exponent %d (|x| up to %d) from the start\n", ln_bound, kActScLow, 448 << -kActScLow);
     }
-    if (hipStreamSynchronize(e->stream) != hipSuccess) { set_err("sync failed"); return false; }   // (the position projections read the load-time tables)
+    if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err("sync failed"); return false; }   // (the position projections read the load-time tables)
     dfree(e, rel_f32); dfree(e, rg); dfree(e, rb); dfree(e, Rf); dfree(e, Rt); dfree(e, vscratch);
     return true;
 }
 
 bool check_shape(const glc_engine* e, int B, int S, int C) {
-    if (B <= 0 || S <= 0 || C < 0) { set_err("forward: B and S must be positive, C non-negative"); return false; }
-    if ((long long)B * round_up(S, 64) > (1ll << 30)) { set_err("forward: batch too large"); return false; }
+    if (B <= 0 || S <= 0 || C < 0) { glc_set_err("forward: B and S must be positive, C non-negative"); return false; }
+    if ((long long)B * round_up(S, 64) > (1ll << 30)) { glc_set_err("forward: batch too large"); return false; }
     (void)e;
     return true;
 }
@@ -1266,33 +1137,33 @@ void glc_delta_table(int S, int bucket_size, int max_position, int32_t* out) {
 }
 
 glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* tensors, int n_tensors, int device, int dtype) {
-    if (!cfg || !tensors) { set_err("engine_create: null argument"); return nullptr; }
-    if (dtype != GLC_F32 && dtype != GLC_BF16 && dtype != GLC_F16) { set_err("engine_create: bad dtype"); return nullptr; }
-    if (n_tensors != glc_num_tensors_cfg(cfg)) { set_err("engine_create: wrong tensor count"); return nullptr; }
-    for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { set_err("engine_create: null tensor"); return nullptr; }
+    if (!cfg || !tensors) { glc_set_err("engine_create: null argument"); return nullptr; }
+    if (dtype != GLC_F32 && dtype != GLC_BF16 && dtype != GLC_F16) { glc_set_err("engine_create: bad dtype"); return nullptr; }
+    if (n_tensors != glc_num_tensors_cfg(cfg)) { glc_set_err("engine_create: wrong tensor count"); return nullptr; }
+    for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { glc_set_err("engine_create: null tensor"); return nullptr; }
     const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT;
-    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb) { set_err("engine_create: unknown backbone"); return nullptr; }
+    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb) { glc_set_err("engine_create: unknown backbone"); return nullptr; }
     if (mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64 || cfg->local_window < 0 || (cfg->local_window > 0 && cfg->global_every < 1) ||
                cfg->rope_theta <= 1.f || (cfg->local_window > 0 && cfg->rope_theta_local <= 1.f))) {
-        set_err("engine_create: ModernBERT backbone needs head_dim 64, local_window >= 0, global_every >= 1 and RoPE bases > 1"); return nullptr;
+        glc_set_err("engine_create: ModernBERT backbone needs head_dim 64, local_window >= 0, global_every >= 1 and RoPE bases > 1"); return nullptr;
     }
-    if (!dec && !mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
+    if (!dec && !mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { glc_set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
     if (dec && ((cfg->head_dim != 64 && cfg->head_dim != 128) || cfg->heads <= 0 || cfg->kv_heads < 0 ||
                 cfg->heads % (cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads) || cfg->rope_theta <= 1.f)) {
-        set_err("engine_create: decoder backbone needs head_dim 64 or 128, heads % kv_heads == 0 and rope_theta > 1"); return nullptr;
+        glc_set_err("engine_create: decoder backbone needs head_dim 64 or 128, heads % kv_heads == 0 and rope_theta > 1"); return nullptr;
     }
     // (ModernBERT: the GeGLU width may be a multiple of 64 — modernbert-large's 2624 — the fused [input | gate] projection is 2I wide)
-    if (cfg->hidden % 128 || cfg->inter % (mb ? 64 : 128)) { set_err("engine_create: hidden and intermediate sizes must be multiples of 128 (ModernBERT: 64)"); return nullptr; }
+    if (cfg->hidden % 128 || cfg->inter % (mb ? 64 : 128)) { glc_set_err("engine_create: hidden and intermediate sizes must be multiples of 128 (ModernBERT: 64)"); return nullptr; }
     if (cfg->pooling < GLC_POOL_FIRST || cfg->pooling > GLC_POOL_LAST || cfg->scorer < GLC_SCORER_DOT || cfg->scorer > GLC_SCORER_MLP) {
-        set_err("engine_create: pooling must be 'first', 'avg' or 'last' and the scorer 'simple', 'weighted-dot' or 'mlp'"); return nullptr;
+        glc_set_err("engine_create: pooling must be 'first', 'avg' or 'last' and the scorer 'simple', 'weighted-dot' or 'mlp'"); return nullptr;
     }
     int ndev = glc_device_count();
-    if (ndev <= 0) { set_err("engine_create: no HIP device visible (this engine has no CPU path)"); return nullptr; }
-    if (device < 0 || device >= ndev) { set_err("engine_create: bad device ordinal"); return nullptr; }
+    if (ndev <= 0) { glc_set_err("engine_create: no HIP device visible (this engine has no CPU path)"); return nullptr; }
+    if (device < 0 || device >= ndev) { glc_set_err("engine_create: bad device ordinal"); return nullptr; }
     HIPCHK(hipSetDevice(device), nullptr);
     if (dec) {
         const size_t NQ = (size_t)cfg->heads * cfg->head_dim, NKV = (size_t)(cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads) * cfg->head_dim;
-        if (NQ % 128 || NKV % 64 || (NQ + 2 * NKV) % 128) { set_err("engine_create: decoder projection widths must be multiples of 128"); return nullptr; }
+        if (NQ % 128 || NKV % 64 || (NQ + 2 * NKV) % 128) { glc_set_err("engine_create: decoder projection widths must be multiples of 128"); return nullptr; }
     }
 
     glc_engine* e = new glc_engine();
@@ -1327,9 +1198,9 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     float* staging = nullptr;      // host f32 -> device T goes through it (upload_as)
     struct StagingGuard { float*& p; ~StagingGuard() { (void)hipFree(p); } } staging_guard{staging};      // (every exit path)
     auto fail = [e]() -> glc_engine* { glc_engine_destroy(e); return nullptr; };
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { set_err("stream create failed"); return fail(); }
-    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { set_err("event create failed"); return fail(); }
-    if (hipMalloc((void**)&staging, staging_floats(e->cfg) * sizeof(float)) != hipSuccess) { set_err("staging alloc failed"); return fail(); }
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { glc_set_err("stream create failed"); return fail(); }
+    if (hipEventCreate(&e->t0) != hipSuccess || hipEventCreate(&e->t1) != hipSuccess) { glc_set_err("event create failed"); return fail(); }
+    if (hipMalloc((void**)&staging, staging_floats(e->cfg) * sizeof(float)) != hipSuccess) { glc_set_err("staging alloc failed"); return fail(); }
     const size_t nemb = (size_t)cfg->vocab * H;           // the token embeddings (HF:518-562)
     e->emb = dmalloc(e, nemb * esize(dtype), false);
     if (!e->emb || !upload_as(e, tensors[0], nemb, e->emb, staging)) return fail();
@@ -1433,7 +1304,7 @@ static int forward_one(glc_engine* e, const int64_t* ids, const int64_t* mask, i
     if (e->profile) prof_collect(e);        // (the attempt whose result is returned)
     for (size_t i = 0, n = (size_t)B * (c_alloc > 0 ? c_alloc : 0); i < n; ++i)
         if (!isfinite(logits[i])) {
-            set_err("forward: non-finite logit (row " + std::to_string(i / c_alloc) + "): an activation left the range of the " +
+            glc_set_err("forward: non-finite logit (row " + std::to_string(i / c_alloc) + "): an activation left the range of the " +
                     (e->dtype == GLC_BF16 ? "bf16" : "f16") + " MFMA operands" +
                     (e->dtype == GLC_F32 ? "; set GLICLASS_F32_GEMM=native GLICLASS_F32_ATTN=native for the fp32-MFMA kernels" : "; use GLICLASS_DTYPE=f32 or bf16"));
             return -1;
@@ -1494,14 +1365,14 @@ static void plan_buckets(const std::vector<int>& len, int max_groups, const Buck
 }
 
 int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, float* logits, int c_alloc, int* c_out) {
-    if (!e || !ids || !mask || (!logits && c_alloc > 0)) { set_err("forward: null argument"); return -1; }
+    if (!e || !ids || !mask || (!logits && c_alloc > 0)) { glc_set_err("forward: null argument"); return -1; }
     if (!check_shape(e, B, S, c_alloc)) return -1;
     // A class token under attention_mask 0 is outside the contract: its hidden state would be a padding-QUERY row (HF: uniform
     // attention over every position), which this engine does not compute — refuse instead of returning a different number.  The
     // reference's tokenizer never produces it (mask 1 on every real token, /root/reference/src/tokenizer.c:77-79).
     for (size_t i = 0, n = (size_t)B * S; i < n; ++i)
         if (mask[i] == 0 && ids[i] == e->cfg.class_token_index) {
-            set_err("forward: a class token (<<LABEL>>) lies under attention_mask 0 (row " + std::to_string(i / S) + ", position " + std::to_string(i % S) + "): not supported");
+            glc_set_err("forward: a class token (<<LABEL>>) lies under attention_mask 0 (row " + std::to_string(i / S) + ", position " + std::to_string(i % S) + "): not supported");
             return -1;
         }
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1554,7 +1425,7 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
 }
 
 int glc_plan_length_buckets(const int* lengths, int B, int max_groups, int hidden, int* order, int* cuts, int* n_groups) {
-    if (!lengths || B <= 0 || hidden <= 0 || !order || !cuts || !n_groups) { set_err("plan_length_buckets: bad args"); return -1; }
+    if (!lengths || B <= 0 || hidden <= 0 || !order || !cuts || !n_groups) { glc_set_err("plan_length_buckets: bad args"); return -1; }
     std::vector<int> len(lengths, lengths + B), ord, cu;
     plan_buckets(len, max_groups, BucketCost(hidden), ord, cu);
     for (int i = 0; i < B; ++i) order[i] = ord[i];
@@ -1571,13 +1442,13 @@ int glc_debug_activation_exponent(const glc_engine* e) { return e ? e->act_sc : 
 long long glc_debug_mx_weight_bytes(const glc_engine* e) { return e ? (long long)e->mx_bytes : -1; }
 
 int glc_engine_set_length_buckets(glc_engine* e, int max_groups) {
-    if (!e || max_groups < 1 || max_groups > 64) { set_err("set_length_buckets: 1..64 groups"); return -1; }
+    if (!e || max_groups < 1 || max_groups > 64) { glc_set_err("set_length_buckets: 1..64 groups"); return -1; }
     e->max_buckets = max_groups;
     return 0;
 }
 
 int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_mask, int B, int S, int C, void* d_logits) {
-    if (!e || !d_ids || !d_mask || (!d_logits && C > 0)) { set_err("forward_device: null argument"); return -1; }
+    if (!e || !d_ids || !d_mask || (!d_logits && C > 0)) { glc_set_err("forward_device: null argument"); return -1; }
     if (!check_shape(e, B, S, C)) return -1;
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device), -1);
@@ -1594,7 +1465,7 @@ int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_ma
 }
 
 int glc_engine_sync(glc_engine* e) {
-    if (!e) { set_err("sync: null engine"); return -1; }
+    if (!e) { glc_set_err("sync: null engine"); return -1; }
     HIPCHK(hipSetDevice(e->device), -1);
     HIPCHK(hipStreamSynchronize(e->stream), -1);
     std::lock_guard<std::mutex> lk(e->mu);
@@ -1604,10 +1475,10 @@ int glc_engine_sync(glc_engine* e) {
         const int what = e->device_invalid;
         e->device_invalid = 0;
         if (what == 1)
-            set_err("sync: a device-resident forward since the last sync had activations beyond the fp8 range of the MX operand images (|x| > 448): its logits are "
+            glc_set_err("sync: a device-resident forward since the last sync had activations beyond the fp8 range of the MX operand images (|x| > 448): its logits are "
                     "not valid; this engine's activation rows now carry exponent -5 (|x| up to 14336) — run the forward again");
         else
-            set_err("sync: a device-resident forward since the last sync had activations beyond the fp8 range of the MX operand images: its logits are "
+            glc_set_err("sync: a device-resident forward since the last sync had activations beyond the fp8 range of the MX operand images: its logits are "
                     "not valid; this engine now runs the split-f16 arithmetic (as GLICLASS_MX=0) — run the forward again");
         return -1;
     }
@@ -1620,9 +1491,9 @@ int glc_engine_sync(glc_engine* e) {
  * the MX operand images — its logits are not valid (NaN-poisoned operand images), the engine has changed its arithmetic as glc_engine_sync
  * would have, run it again; -1 = error.  The stream must be idle: this call does not wait. */
 int glc_engine_device_forward_valid(glc_engine* e) {
-    if (!e) { set_err("device_forward_valid: null engine"); return -1; }
+    if (!e) { glc_set_err("device_forward_valid: null engine"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
-    if (hipStreamQuery(e->stream) != hipSuccess) { set_err("device_forward_valid: the engine's stream still has work queued — wait for it first (or call glc_engine_sync)"); return -1; }
+    if (hipStreamQuery(e->stream) != hipSuccess) { glc_set_err("device_forward_valid: the engine's stream still has work queued — wait for it first (or call glc_engine_sync)"); return -1; }
     if (e->fp8_device_pending) settle_device_range_check(e);
     const int bad = e->device_invalid;
     e->device_invalid = 0;
@@ -1630,10 +1501,10 @@ int glc_engine_device_forward_valid(glc_engine* e) {
 }
 
 void* glc_device_malloc(glc_engine* e, size_t bytes) {
-    if (!e) { set_err("device_malloc: null engine"); return nullptr; }
+    if (!e) { glc_set_err("device_malloc: null engine"); return nullptr; }
     if (hipSetDevice(e->device) != hipSuccess) return nullptr;
     void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { set_err("device_malloc failed"); return nullptr; }
+    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { glc_set_err("device_malloc failed"); return nullptr; }
     return p;
 }
 void glc_device_free(glc_engine* e, void* p) { if (e && p) { (void)hipSetDevice(e->device); (void)hipFree(p); } }
@@ -1684,7 +1555,7 @@ int glc_profile_read(glc_engine* e, const char** names, float* total_ms, int* la
 }
 
 int glc_debug_set_group_split(glc_engine* e, int mode) {
-    if (!e || mode < 0 || mode > 2) { set_err("group_split: 0 off, 1 auto, 2 whenever the shapes allow"); return -1; }
+    if (!e || mode < 0 || mode > 2) { glc_set_err("group_split: 0 off, 1 auto, 2 whenever the shapes allow"); return -1; }
     e->gs_mode = mode;
     return 0;
 }
@@ -1692,7 +1563,7 @@ int glc_debug_last_forward_group_split(const glc_engine* e) { return e ? (e->las
 /* MX cross-term pipeline on / off (needs the GX weight copies: an engine created under GLICLASS_MX=1 or =build). */
 int glc_debug_set_mx(glc_engine* e, int on) {
     if (!e) return -1;
-    if (on && !e->mx_built) { set_err("set_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1; }
+    if (on && !e->mx_built) { glc_set_err("set_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
     e->mx = on != 0;
     if (on) { e->fp8_sticky_off = false; e->fp8_streak = 0; e->act_sc = 0; }      // (a developer switching MX back on also clears the range guard's verdict)
@@ -1703,38 +1574,8 @@ int glc_debug_last_forward_mx_attention(const glc_engine* e) { return e ? (e->la
 /* MX pipeline: attention on MX tiles (1, default) or on split-f16 units (0). */
 int glc_debug_set_mx_attention(glc_engine* e, int on) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); e->mx_attn = on != 0; return 0; }
 /* Developer: stop the next forwards after stage 10 * layer + k (k = 0 QKV, 1 attention, 2 attention-output, 3 FFN1, 4 FFN2 + LayerNorm;
- * -1 = run to the end; logits are garbage when stopped) and read workspace rows as fp32: which = 0 X, 1 H1, 2 CTX, 3 FF (row formats
- * decoded: GX after an MX forward, GS after a group-split one), 4 T1 (plain fp32), 5 statsA, 6 statsB (2 floats per row). */
+ * -1 = run to the end; logits are garbage when stopped); glc_debug_read_workspace (engine_debug.hip) then reads the workspace rows. */
 int glc_debug_set_stop(glc_engine* e, int stage) { if (!e) return -1; e->debug_stop = stage; return 0; }
-int glc_debug_read_workspace(glc_engine* e, int which, int rows, float* out) {
-    if (!e || !out || rows <= 0 || which < 0 || which > 9) { set_err("read_workspace: bad args"); return -1; }
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHK(hipSetDevice(e->device), -1);
-    HIPCHK(hipStreamSynchronize(e->stream), -1);
-    if (rows > e->capM) { set_err("read_workspace: more rows than the workspace holds"); return -1; }
-    const int H = e->cfg.hidden, I = e->cfg.inter;
-    if (which >= 7) { HIPCHK(hipMemcpy(out, which == 7 ? e->Qh : which == 8 ? e->Kh : e->Vt, (size_t)rows * e->cfg.hidden * 4, hipMemcpyDeviceToHost), -1); return 0; }   // raw units
-    if (which >= 5) { HIPCHK(hipMemcpy(out, which == 5 ? e->statsA : e->statsB, (size_t)rows * 8, hipMemcpyDeviceToHost), -1); return 0; }
-    const void* src = which == 0 ? e->X : which == 1 ? e->H1 : which == 2 ? e->CTX : which == 3 ? e->FF : e->T1;
-    const int W = which == 3 ? I : H;
-    std::vector<unsigned char> raw((size_t)rows * W * 4);
-    HIPCHK(hipMemcpy(raw.data(), src, raw.size(), hipMemcpyDeviceToHost), -1);
-    if (which == 4 || !e->last_gs) { memcpy(out, raw.data(), raw.size()); return 0; }
-    for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < W; ++c) {
-            const unsigned char* g = raw.data() + ((size_t)r * W + (c & ~31)) * 4;
-            _Float16 hi, lo; memcpy(&hi, g + 2 * (c & 31), 2);
-            float v = (float)hi;
-            if (e->last_mx) {
-                const unsigned char b = g[64 + 16 * ((c & 31) >> 3) + (c & 7)];
-                const int sg = b >> 7, ex = (b >> 3) & 15, mn = b & 7;
-                const float l8 = ex == 0 ? ldexpf((float)mn, -9) : ldexpf(1.0f + mn / 8.0f, ex - 7);
-                v += (sg ? -l8 : l8) * ldexpf(1.0f, -GLC_GX_SHIFT - e->act_sc);
-            } else { memcpy(&lo, g + 64 + 2 * (c & 31), 2); v += (float)lo; }
-            out[(size_t)r * W + c] = v;
-        }
-    return 0;
-}
 /* Group-split pipeline with LayerNorm folded into the GEMMs (1, default) or as kernels of its own (0).  The folded weights are built
  * at load unless GLC_LNF=0 was set then; without them the switch has no effect. */
 int glc_debug_last_forward_ln_folded(const glc_engine* e) { return e ? (e->last_lnf ? 1 : 0) : -1; }
@@ -1746,7 +1587,7 @@ int glc_debug_set_ln_fused(glc_engine* e, int on) {
 }
 /* Precision budget (developer): round operand groups of the default mode's group-split pipeline to f16 (PM_* bits of glc_kernels.h). */
 int glc_debug_set_precision_mask(glc_engine* e, int mask) {
-    if (!e || mask < 0 || mask >= (1 << 15)) { set_err("precision_mask: 15 bits"); return -1; }
+    if (!e || mask < 0 || mask >= (1 << 15)) { glc_set_err("precision_mask: 15 bits"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
     e->prec_mask = mask;
     return 0;
@@ -1756,499 +1597,9 @@ int glc_debug_set_gemm_full_lines(int on) { glc_gemm_set_full_lines(on); return 
 int glc_debug_keep_hidden(glc_engine* e, int on) { if (!e) return -1; e->keep_hidden = on != 0; return 0; }
 int glc_engine_set_prune_last_layer(glc_engine* e, int on) { if (!e) return -1; e->prune_last = on != 0; return 0; }
 int glc_debug_set_attention_impl(glc_engine* e, int impl) {
-    if (!e || impl < 0 || impl > 3) { set_err("bad attention impl"); return -1; }
+    if (!e || impl < 0 || impl > 3) { glc_set_err("bad attention impl"); return -1; }
     e->attn_impl = impl;
     return 0;
-}
-int glc_debug_get_hidden(glc_engine* e, int which, float* out, size_t out_elems) {
-    if (!e || !out) { set_err("get_hidden: null"); return -1; }
-    std::lock_guard<std::mutex> lk(e->mu);
-    const int B = e->lastB, S = e->lastS, Sp = e->lastSp, H = e->cfg.hidden;
-    if (!e->hidden_dump || B == 0 || which < 0 || which > e->cfg.layers) { set_err("get_hidden: nothing recorded"); return -1; }
-    if (out_elems < (size_t)B * S * H) { set_err("get_hidden: output too small"); return -1; }
-    HIPCHK(hipSetDevice(e->device), -1);
-    const size_t M = (size_t)B * Sp, es = esize(e->dtype);
-    float* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, M * H * sizeof(float)), -1);
-    const char* m = glc_launch_to_f32(e->stream, e->dtype, (char*)e->hidden_dump + (size_t)which * M * H * es, tmp, M * H);
-    if (m) { (void)hipFree(tmp); set_err(m); return -1; }
-    hipError_t r = hipMemcpy2DAsync(out, (size_t)S * H * sizeof(float), tmp, (size_t)Sp * H * sizeof(float), (size_t)S * H * sizeof(float), B,
-                                    hipMemcpyDeviceToHost, e->stream);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-    (void)hipFree(tmp);
-    if (r != hipSuccess) { set_err(std::string("get_hidden: ") + hipGetErrorString(r)); return -1; }
-    return 0;
-}
-
-/* Developer microbenchmark: time `iters` launches of one GEMM shape on random 16-bit data (HIP events).
- * which: 0 = auto (256-tile when possible), 1 = force the 128x128 kernel.  Returns ms per launch or <0. */
-float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iters, int which) {
-    // which == 6: the group-split fp32-mode kernel (rows of [32 hi | 32 lo] f16 groups, 4 bytes per element; any engine dtype)
-    const int which_in = which;
-    if (which >= 100) which %= 100;
-    const bool mxb = which == 9;                      // the MX cross-term kernel on GX rows (gemm256x.hip); which = 100 (1 + prio) + 9: wave priority policy prio
-    const bool gsb = which == 6 || which == 8 || mxb;
-    const int mx_ws = glc_gx_weight_exponent(0.5f);
-    if (!e || M <= 0 || N <= 0 || K <= 0 || iters <= 0 || which_in >= 1000 || (which >= 10 && which <= 14) || (e->dtype == GLC_F32 && !gsb) || epi < EPI_BIAS || epi > EPI_RESID) {
-        set_err("gemm_bench: bad args"); return -1.f;
-    }
-    if (M % 256 || N % 256 || K % 64) { set_err("gemm_bench: M,N %256, K %64 required"); return -1.f; }
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHK(hipSetDevice(e->device), -1.f);
-    const size_t es = gsb ? 4 : 2;
-    void *A = nullptr, *W = nullptr, *C = nullptr, *R = nullptr; float *bias = nullptr, *tmp = nullptr;
-    const size_t nA = (size_t)M * K, nW = (size_t)N * K, nC = (size_t)M * N;
-    const size_t nmax = nA > nW ? (nA > nC ? nA : nC) : (nW > nC ? nW : nC);
-    float ms = -1.f;
-    do {
-        if (hipMalloc(&A, nA * es) || hipMalloc(&W, nW * es) || hipMalloc(&C, nC * es) || hipMalloc(&R, nC * es) ||
-            hipMalloc((void**)&bias, N * sizeof(float)) || hipMalloc((void**)&tmp, nmax * sizeof(float))) { set_err("gemm_bench: alloc failed"); break; }
-        std::vector<float> h(nmax);
-        unsigned s = 12345u;
-        const char* zenv = glc_dev_env("GLC_BENCH_DATA");       // developer: "zero" = all-zero operands, "const" = one value everywhere (how much of the time is the power envelope?)
-        for (size_t i = 0; i < nmax; ++i) { s = s * 1664525u + 1013904223u; h[i] = zenv && zenv[0] == 'z' ? 0.f : zenv && zenv[0] == 'c' ? 0.37f : ((float)(s >> 8) / 8388608.f - 1.f) * 0.5f; }
-        if (hipMemcpy(tmp, h.data(), nmax * sizeof(float), hipMemcpyHostToDevice)) { set_err("gemm_bench: copy failed"); break; }
-        if (gsb) {      // fp32 values, split in place into the group-split image (or the GX image)
-            if (hipMemcpyAsync(A, tmp, nA * 4, hipMemcpyDeviceToDevice, e->stream) || hipMemcpyAsync(W, tmp, nW * 4, hipMemcpyDeviceToDevice, e->stream) ||
-                hipMemcpyAsync(R, tmp, nC * 4, hipMemcpyDeviceToDevice, e->stream)) { set_err("gemm_bench: copy failed"); break; }
-            if (mxb ? (glc_launch_to_gx(e->stream, A, nA, 0, 0) || glc_launch_to_gx(e->stream, W, nW, mx_ws, 1) || glc_launch_to_gx(e->stream, R, nC, 0, 0))
-                    : (glc_launch_presplit(e->stream, A, nA) || glc_launch_presplit(e->stream, W, nW) || glc_launch_presplit(e->stream, R, nC))) { set_err("gemm_bench: split failed"); break; }
-        } else
-        if (glc_launch_convert(e->stream, e->dtype, tmp, A, nA) || glc_launch_convert(e->stream, e->dtype, tmp, W, nW) ||
-            glc_launch_convert(e->stream, e->dtype, tmp, R, nC)) { set_err("gemm_bench: convert failed"); break; }
-        if (hipMemcpyAsync(bias, tmp, N * sizeof(float), hipMemcpyDeviceToDevice, e->stream)) break;
-        GemmArgs g; g.A = A; g.W = W; g.bias = bias; g.C = C; g.resid = R; g.Mpad = M; g.N = N; g.K = K; g.mx_ws = mx_ws;
-        if (mxb && which_in >= 100) g.prio_mode = which_in / 100 - 1;      // which = 100 (1 + prio) + 9
-        const char* m = nullptr;
-        auto launch = [&]() -> const char* { return mxb ? glc_launch_gemm256x(e->stream, epi, g) : gsb ? glc_launch_gemm256s_gs(e->stream, epi, g) : which == 1 ? glc_launch_gemm(e->stream, e->dtype, epi, g) : (which == 5 || which == 7) ? glc_launch_gemm256s(e->stream, e->dtype, epi, g) : glc_launch_gemm_auto(e->stream, e->dtype, epi, g); };
-        for (int i = 0; i < 2 && !m; ++i) m = launch();
-        if (m) { set_err(m); break; }
-        if (hipEventRecord(e->t0, e->stream)) break;
-        for (int i = 0; i < iters; ++i) launch();
-        if (hipEventRecord(e->t1, e->stream) || hipEventSynchronize(e->t1)) { set_err("gemm_bench: sync failed"); break; }
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, e->t0, e->t1)) break;
-        ms = t / iters;
-        if (which == 7 || which == 8) {     // diagnostic: one stamped launch of the full-line 256-tile kernel (7: 16-bit operands, 8: group-split), EPI_BIAS
-            unsigned long long* dbuf = nullptr;
-            const size_t ns = 64 * 8 * 14;
-            if (hipMalloc((void**)&dbuf, ns * sizeof(unsigned long long)) == hipSuccess) {
-                (void)hipMemsetAsync(dbuf, 0, ns * sizeof(unsigned long long), e->stream);
-                GemmArgs gd = g; gd.stamps = dbuf;
-                const char* dm = which == 8 ? glc_launch_gemm256s_gs(e->stream, EPI_BIAS, gd) : glc_launch_gemm256s(e->stream, e->dtype, EPI_BIAS, gd);
-                (void)hipStreamSynchronize(e->stream);
-                std::vector<unsigned long long> hs(ns);
-                if (!dm && hipMemcpy(hs.data(), dbuf, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                    for (int grp = 0; grp < 2; ++grp) {       // wave group 0 (waves 0-3) / the late group (waves 4-7)
-                        double sg[12] = {0};
-                        for (int b = 0; b < 64; ++b) for (int w = 4 * grp; w < 4 * grp + 4; ++w) for (int k = 0; k < 12; ++k) sg[k] += (double)hs[((size_t)b * 8 + w) * 12 + k];
-                        const double n = 64 * 4, ng = sg[11] / n > 0 ? sg[11] / n : 1;
-                        fprintf(stderr, "[gemm256s stamps M=%d N=%d K=%d %s, waves %d-%d] cycles per group and wave: E: dma %.0f reads+wait %.0f barrier %.0f mfma %.0f barrier %.0f | "
-                                        "O: (dma %.0f) reads+wait %.0f barrier %.0f mfma %.0f barrier %.0f | total %.0f | clock %.0f MHz\n", M, N, K, which == 8 ? "group-split" : "16-bit", 4 * grp, 4 * grp + 3,
-                                sg[0] / n / ng, sg[1] / n / ng, sg[2] / n / ng, sg[3] / n / ng, sg[4] / n / ng, sg[5] / n / ng, sg[6] / n / ng, sg[7] / n / ng, sg[8] / n / ng, sg[9] / n / ng,
-                                (sg[0] + sg[1] + sg[2] + sg[3] + sg[4] + sg[5] + sg[6] + sg[7] + sg[8] + sg[9]) / n / ng, sg[10] / n / 10.0);
-                    }
-                    double pro = 0, epi = 0;
-                    for (size_t i = 0; i < 64 * 8; ++i) { pro += (double)hs[64 * 8 * 12 + 2 * i]; epi += (double)hs[64 * 8 * 12 + 2 * i + 1]; }
-                    fprintf(stderr, "[gemm256s stamps] per tile and wave: entry -> loop %.0f cycles, loop end -> stores retired %.0f cycles\n", pro / (64 * 8), epi / (64 * 8));
-                } else if (dm) fprintf(stderr, "[gemm256s stamps] %s\n", dm);
-                (void)hipFree(dbuf);
-            }
-        }
-    } while (0);
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(C); (void)hipFree(R); (void)hipFree(bias); (void)hipFree(tmp);
-    return ms;
-}
-
-/* Developer check: the MX cross-term GEMM (gemm256x.hip) against the split-f16 GEMM (gemm256s.hip, GS) on the same random fp32 operands
- * (A ~ U(-a_amp, a_amp), W ~ U(-w_amp, w_amp), bias), every epilogue path:
- *   mode 0  EPI_BIAS, plain fp32 outputs                      mode 1  EPI_GELU with the LayerNorm fold (a_stats, ln_c), GX / GS row outputs
- *   mode 2  EPI_RESID, raw residual rows + r_stats / gamma / beta, raw row outputs + ln_part          mode 3  EPI_RESID, plain fp32 out
- *   mode 4  EPI_QKV with the fold (N = 3 H, Sp = 256): Q, K, V^T split-f16 units
- * out[0] = max |mx - gs|, out[1] = max |gs|, out[2] = rms(mx - gs), out[3] = rms(gs) over the decoded outputs (mode 2: + the ln_part
- * sums in out[4] = max |diff|).  Returns 0 or < 0. */
-int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, float w_amp, int mode, double* out) {
-    if (!e || !out || M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 32 || mode < 0 || mode > 4) { set_err("gemm_mx_check: bad args"); return -1; }
-    if (mode == 4 && (N % 768 || M % 256)) { set_err("gemm_mx_check: the QKV mode needs N = 3 H, H % 256 == 0"); return -1; }
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHK(hipSetDevice(e->device), -1);
-    const size_t nA = (size_t)M * K, nW = (size_t)N * K, nC = (size_t)M * N;
-    float *A = nullptr, *W = nullptr, *A2 = nullptr, *W2 = nullptr, *C0 = nullptr, *C1 = nullptr, *R0 = nullptr, *R1 = nullptr, *bias = nullptr, *lnc = nullptr, *gam = nullptr, *bet = nullptr;
-    float2 *st = nullptr, *lp0 = nullptr, *lp1 = nullptr;
-    int rc = -1;
-    do {
-        if (hipMalloc((void**)&A, nA * 4) || hipMalloc((void**)&W, nW * 4) || hipMalloc((void**)&A2, nA * 4) || hipMalloc((void**)&W2, nW * 4) ||
-            hipMalloc((void**)&C0, nC * 4) || hipMalloc((void**)&C1, nC * 4) || hipMalloc((void**)&R0, nC * 4) || hipMalloc((void**)&R1, nC * 4) ||
-            hipMalloc((void**)&bias, (size_t)N * 4) || hipMalloc((void**)&lnc, (size_t)N * 4) || hipMalloc((void**)&gam, (size_t)N * 4) || hipMalloc((void**)&bet, (size_t)N * 4) ||
-            hipMalloc((void**)&st, (size_t)M * 8) || hipMalloc((void**)&lp0, (size_t)M * (N / 64) * 8) || hipMalloc((void**)&lp1, (size_t)M * (N / 64) * 8)) { set_err("gemm_mx_check: alloc failed"); break; }
-        std::vector<float> ha(nA), hw(nW), hb(N), hc(N), hg(N), hbe(N), hr(nC);
-        std::vector<float2> hst(M);
-        unsigned s = 777u + 13u * mode;
-        auto rnd = [&]() { s = s * 1664525u + 1013904223u; return (float)(s >> 8) / 8388608.f - 1.f; };
-        const bool special = a_amp < 0.f;      // developer: a = 1 + 2^-12 (hi 1, lo 2^-12), w = 1, no bias: every output = K (1 + 2^-12) iff the a_lo w_hi terms arrive
-        const int spec = special ? (int)(-a_amp + 0.5f) : 0;      // 1: a = 1 + 2^-12, w = 1; 2: a = 1, w = 1 + 2^-12; 3: both; 4: a = 3 + 3 2^-12 (hi 3, lo), w = 1
-        if (special) a_amp = 1.f;
-        for (auto& v : ha) v = rnd() * a_amp;
-        for (auto& v : hw) v = rnd() * w_amp;
-        for (auto& v : hr) v = rnd() * a_amp;
-        for (int n = 0; n < N; ++n) { hb[n] = rnd() * 0.1f; hc[n] = rnd() * 0.05f; hg[n] = 1.f + 0.3f * rnd(); hbe[n] = 0.2f * rnd(); }
-        for (int m = 0; m < M; ++m) hst[m] = make_float2(0.1f * rnd() * a_amp, (0.5f + 0.4f * rnd()) / a_amp);
-        if (special) { const float d = ldexpf(1.f, -12); for (auto& v : ha) v = spec == 2 ? 1.0f : spec == 4 ? 3.0f + 3.0f * d : 1.0f + d; for (auto& v : hw) v = spec >= 2 && spec <= 3 ? 1.0f + d : 1.0f; for (auto& v : hb) v = 0.f; }
-        if (hipMemcpy(A, ha.data(), nA * 4, hipMemcpyHostToDevice) || hipMemcpy(W, hw.data(), nW * 4, hipMemcpyHostToDevice) ||
-            hipMemcpy(A2, ha.data(), nA * 4, hipMemcpyHostToDevice) || hipMemcpy(W2, hw.data(), nW * 4, hipMemcpyHostToDevice) ||
-            hipMemcpy(R0, hr.data(), nC * 4, hipMemcpyHostToDevice) || hipMemcpy(R1, hr.data(), nC * 4, hipMemcpyHostToDevice) ||
-            hipMemcpy(bias, hb.data(), (size_t)N * 4, hipMemcpyHostToDevice) || hipMemcpy(lnc, hc.data(), (size_t)N * 4, hipMemcpyHostToDevice) ||
-            hipMemcpy(gam, hg.data(), (size_t)N * 4, hipMemcpyHostToDevice) || hipMemcpy(bet, hbe.data(), (size_t)N * 4, hipMemcpyHostToDevice) ||
-            hipMemcpy(st, hst.data(), (size_t)M * 8, hipMemcpyHostToDevice) || hipMemset(C0, 0, nC * 4) || hipMemset(C1, 0, nC * 4)) { set_err("gemm_mx_check: copy failed"); break; }
-        const int ws = glc_gx_weight_exponent(w_amp);
-        const char* m = glc_launch_presplit(e->stream, A, nA);
-        if (!m) m = glc_launch_presplit(e->stream, W, nW);
-        if (!m) m = glc_launch_presplit(e->stream, R0, nC);
-        if (!m) m = glc_launch_to_gx(e->stream, A2, nA, 0, 0);
-        if (!m) m = glc_launch_to_gx(e->stream, W2, nW, ws, 1);
-        if (!m) m = glc_launch_to_gx(e->stream, R1, nC, 0, 0);
-        GemmArgs g; g.bias = bias; g.Mpad = M; g.N = N; g.K = K;
-        int epi = EPI_BIAS;
-        if (mode == 0) g.gs_c_plain = 1;
-        if (mode == 1) { epi = EPI_GELU; g.a_stats = st; g.ln_c = lnc; }
-        if (mode == 2 || mode == 3) { epi = EPI_RESID; if (mode == 2) { g.r_stats = st; g.r_gamma = gam; g.r_beta = bet; } }
-        if (mode == 4) { epi = EPI_QKV; g.a_stats = st; g.ln_c = lnc; g.H = N / 3; g.nh = g.H / 64; g.Sp = 256; g.Mvalid = M; g.qkv_split = 1; }
-        const size_t third = nC / 3;
-        g.A = A; g.W = W; g.C = C0; g.resid = R0; if (mode == 2) g.ln_part = lp0;
-        if (mode == 4) { g.Qh = C0; g.Kh = C0 + third; g.Vt = C0 + 2 * third; }
-        if (!m) m = glc_launch_gemm256s_gs(e->stream, epi, g);
-        g.A = A2; g.W = W2; g.C = C1; g.resid = R1; g.mx_ws = ws; if (mode == 2) g.ln_part = lp1;
-        if (mode == 4) { g.Qh = C1; g.Kh = C1 + third; g.Vt = C1 + 2 * third; }
-        if (!m) m = glc_launch_gemm256x(e->stream, epi, g);
-        if (m) { set_err(m); break; }
-        std::vector<float> c0(nC), c1(nC);
-        if (hipStreamSynchronize(e->stream) || hipMemcpy(c0.data(), C0, nC * 4, hipMemcpyDeviceToHost) || hipMemcpy(c1.data(), C1, nC * 4, hipMemcpyDeviceToHost)) { set_err("gemm_mx_check: readback failed"); break; }
-        // decode the row formats on the host: GS group = [32 hi halves | 32 lo halves]; GX group = [32 hi halves | 32 lo8 | 32 hi8]; QKV units = [8 hi | 8 lo] halves
-        auto half_at = [](const float* base, size_t hidx) { _Float16 hv; memcpy(&hv, reinterpret_cast<const unsigned char*>(base) + 2 * hidx, 2); return (float)hv; };
-        auto fp8_at = [](const float* base, size_t bidx) {
-            const unsigned char b = reinterpret_cast<const unsigned char*>(base)[bidx];
-            const int sg = b >> 7, ex = (b >> 3) & 15, mn = b & 7;
-            const float v = ex == 0 ? ldexpf((float)mn, -9) : ldexpf(1.0f + mn / 8.0f, ex - 7);
-            return sg ? -v : v;
-        };
-        const bool rows_gs = mode == 1 || mode == 2, units = mode == 4;
-        double md = 0, mr = 0, sd = 0, sr = 0;
-        for (size_t i = 0; i < nC; ++i) {
-            double v0, v1;
-            if (rows_gs) {
-                const size_t row = i / N, col = i % N, grp = col >> 5, e5 = col & 31;
-                v0 = half_at(c0.data(), (row * N + grp * 32) * 2 + e5) + half_at(c0.data(), (row * N + grp * 32) * 2 + 32 + e5);
-                v1 = half_at(c1.data(), (row * N + grp * 32) * 2 + e5) + fp8_at(c1.data(), (row * N + grp * 32) * 4 + 64 + 16 * (e5 >> 3) + (e5 & 7)) * ldexp(1.0, -GLC_GX_SHIFT);
-            } else if (units) {
-                const size_t u = i >> 3, j = i & 7;
-                v0 = half_at(c0.data(), u * 16 + j) + half_at(c0.data(), u * 16 + 8 + j);
-                v1 = half_at(c1.data(), u * 16 + j) + half_at(c1.data(), u * 16 + 8 + j);
-            } else { v0 = c0[i]; v1 = c1[i]; }
-            const double d = v1 - v0;
-            if (!(fabs(d) <= md)) md = fabs(d);
-            if (fabs(v0) > mr) mr = fabs(v0);
-            sd += d * d; sr += v0 * v0;
-        }
-        out[0] = md; out[1] = mr; out[2] = sqrt(sd / nC); out[3] = sqrt(sr / nC); out[4] = 0;
-        if (special) fprintf(stderr, "[gemm_mx_check special] K = %d: split-f16 C[0] = %.6f, MX leg C[0] = %.6f C[1] = %.6f C[N+5] = %.6f; (case %d)\n", K, c0[0], c1[0], c1[1], c1[N + 5], spec);
-        if (mode == 2) {
-            std::vector<float2> p0((size_t)M * (N / 64)), p1(p0.size());
-            if (hipMemcpy(p0.data(), lp0, p0.size() * 8, hipMemcpyDeviceToHost) || hipMemcpy(p1.data(), lp1, p1.size() * 8, hipMemcpyDeviceToHost)) { set_err("gemm_mx_check: readback failed"); break; }
-            double pd = 0;
-            for (size_t i = 0; i < p0.size(); ++i) { pd = fmax(pd, fabs((double)p0[i].x - p1[i].x)); pd = fmax(pd, fabs((double)p0[i].y - p1[i].y) / (1.0 + fabs(p0[i].y))); }
-            out[4] = pd;
-        }
-        rc = 0;
-    } while (0);
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(A2); (void)hipFree(W2); (void)hipFree(C0); (void)hipFree(C1); (void)hipFree(R0); (void)hipFree(R1);
-    (void)hipFree(bias); (void)hipFree(lnc); (void)hipFree(gam); (void)hipFree(bet); (void)hipFree(st); (void)hipFree(lp0); (void)hipFree(lp1);
-    return rc;
-}
-
-}  // extern "C"
-namespace {
-// device buffers of one glc_debug_gemm_run call (freed when it returns)
-struct RunBufs {
-    std::vector<void*> v;
-    ~RunBufs() { for (void* p : v) (void)hipFree(p); }
-    void* get(size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr; v.push_back(p); return p; }
-    void* up(const void* h, size_t bytes) { void* p = get(bytes); if (p && hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr; return p; }
-};
-constexpr size_t RUN_GUARD = 1u << 20;      // bytes of guard before and after every output
-// bytes of output i (C, or Qh / Kh / Vt) the launch may write; 0 = that output does not exist (or the shape is one every launcher refuses)
-size_t gemm_run_out_bytes(const glc_gemm_run& r, int dtype, int i) {
-    const bool wide = r.kernel == GLC_GEMM_RUN_GS || r.kernel == GLC_GEMM_RUN_MX;       // GS / GX rows, split units, MX tiles and plain fp32: 4 bytes per element
-    const size_t es = wide ? 4 : esize(dtype);
-    if (r.epi == EPI_QKV || r.epi == EPI_QKVR) {
-        if (r.Sp <= 0 || r.Mvalid <= 0) return 0;
-        const size_t rows = (size_t)std::min(r.Mvalid, r.Mpad), B = (rows + r.Sp - 1) / r.Sp;
-        if (r.epi == EPI_QKVR) return r.nq > 0 && r.nkv > 0 ? B * (size_t)(i == 0 ? r.nq : r.nkv) * r.Sp * 128 * 4 : 0;
-        return r.nh > 0 ? B * (size_t)r.nh * r.Sp * 64 * es : 0;
-    }
-    if (i > 0) return 0;
-    const bool glu = r.epi == EPI_SWIGLU || r.epi == EPI_GEGLU;
-    return (size_t)r.Mpad * (size_t)(glu ? r.N / 2 : r.N) * es;
-}
-}  // namespace
-extern "C" {
-
-/* Kernel-level tests: one launcher call on caller-supplied operands, raw bytes back (include/gliclass_hip.h). */
-int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r) {
-    if (!e || !r || r->kernel < GLC_GEMM_RUN_128 || r->kernel > GLC_GEMM_RUN_AUTO || r->epi < EPI_BIAS || r->epi > EPI_GEGLU || r->Mpad <= 0 || r->N <= 0 || r->K <= 0 ||
-        r->Mpad > (1 << 20) || r->N > (1 << 20) || r->K > (1 << 20) || !r->A || !r->W || (r->W2 && r->kernel != GLC_GEMM_RUN_128) || r->ws_bytes > (1ull << 30)) {
-        set_err("gemm_run: bad args"); return -1;
-    }
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHK(hipSetDevice(e->device), -1);
-    const int dtype = e->dtype, kern = r->kernel;
-    const bool gs = kern == GLC_GEMM_RUN_GS, mx = kern == GLC_GEMM_RUN_MX;
-    const size_t es = gs || mx ? 4 : esize(dtype);
-    auto up32 = [](size_t n) { return (n + 31) / 32 * 32; };      // the group converters take whole 32-groups (a row length they cut wrongly is one the launcher refuses)
-    const size_t nA = (size_t)r->Mpad * r->K, nW = (size_t)r->N * r->K, nC = (size_t)r->Mpad * r->N;
-    RunBufs bufs;
-    hipStream_t st = e->stream;
-    const char* msg = nullptr;
-    bool own = false;                               // msg is this entry's own failure (allocation, copy), not a refusal
-    // fp32 host values -> the operand image this kernel reads; role: 0 = activation rows (A, resid), 1 = weight rows
-    auto encode = [&](const float* h, size_t n, int role, bool plain) -> void* {
-        const size_t n32 = up32(n);
-        float* tmp = (float*)bufs.get(n32 * 4);
-        if (!tmp || hipMemsetAsync(tmp, 0, n32 * 4, st) != hipSuccess || hipMemcpyAsync(tmp, h, n * 4, hipMemcpyHostToDevice, st) != hipSuccess) { msg = "gemm_run: operand upload failed"; own = true; return nullptr; }
-        if (plain) return tmp;
-        if (gs) { msg = glc_launch_presplit(st, tmp, n32); return msg ? nullptr : tmp; }
-        if (mx) {
-            if (role == 1 && r->w_from_gs) {        // the engine's path: the split-f16 copy first, the GX copy from it
-                void* gx = bufs.get(n32 * 4);
-                if (!gx) { msg = "gemm_run: alloc failed"; own = true; return nullptr; }
-                msg = glc_launch_presplit(st, tmp, n32);
-                if (!msg) msg = glc_launch_gs_to_gx(st, tmp, gx, n32, r->mx_ws);
-                return msg ? nullptr : gx;
-            }
-            msg = glc_launch_to_gx(st, tmp, n32, role == 1 ? r->mx_ws : r->act_sc, role);
-            return msg ? nullptr : tmp;
-        }
-        if (dtype == GLC_F32) {
-            if (role == 1 && r->w_presplit) msg = glc_launch_presplit(st, tmp, n32);
-            return msg ? nullptr : tmp;
-        }
-        void* img = bufs.get(n32 * 2);
-        if (!img) { msg = "gemm_run: alloc failed"; own = true; return nullptr; }
-        msg = glc_launch_convert(st, dtype, tmp, img, n);
-        return msg ? nullptr : img;
-    };
-    auto fail = [&](const char* m, int rc) { (void)hipStreamSynchronize(st); set_err(m); return rc; };
-    GemmArgs g;
-    g.Mpad = r->Mpad; g.N = r->N; g.K = r->K; g.m_split = r->m_split; g.Mvalid = r->Mvalid; g.Sp = r->Sp; g.nh = r->nh; g.H = r->H; g.nq = r->nq; g.nkv = r->nkv;
-    g.qscale = r->qscale; g.qkv_skip_q = r->qkv_skip_q; g.qkv_split = r->qkv_split; g.qkv_mxt = r->qkv_mxt; g.gs_c_plain = r->gs_c_plain; g.gs_resid_plain = r->gs_resid_plain;
-    g.perm_cols = r->perm_cols; g.prec = r->prec; g.mx_ws = r->mx_ws; g.act_sc = r->act_sc; g.gx_rows = r->gx_rows;
-    g.w_presplit = kern == GLC_GEMM_RUN_128 && dtype == GLC_F32 && r->w_presplit;
-    g.A = encode(r->A, nA, 0, false);
-    if (!msg) g.W = encode(r->W, nW, 1, false);
-    if (!msg && r->W2) g.W2 = encode(r->W2, nW, 1, false);
-    if (!msg && r->resid) g.resid = encode(r->resid, nC, 0, gs && r->gs_resid_plain);
-    if (msg) return fail(msg, own ? -1 : -2);      // a converter's refusal counts as the launcher's: nothing has been launched
-    auto upf = [&](const float* h, size_t n) -> const float* { if (!h) return nullptr; const float* p = (const float*)bufs.up(h, n * 4); if (!p) msg = "gemm_run: upload failed"; return p; };
-    g.bias = upf(r->bias, r->N); g.bias2 = upf(r->bias2, r->N); g.ln_c = upf(r->ln_c, r->N); g.r_gamma = upf(r->r_gamma, r->N); g.r_beta = upf(r->r_beta, r->N);
-    g.a_stats = (const float2*)upf(r->a_stats, 2 * (size_t)r->Mpad); g.r_stats = (const float2*)upf(r->r_stats, 2 * (size_t)r->Mpad);
-    if (r->rope_cs) { if (r->Sp <= 0 || r->Sp > (1 << 16)) return fail("gemm_run: bad args", -1); g.rope_cs = upf(r->rope_cs, (size_t)r->Sp * 128); }
-    if (r->q_tile_flag) {
-        const size_t nf = (size_t)r->Mpad / 32 + 8;
-        unsigned char* f = (unsigned char*)bufs.get(nf);
-        if (!f || hipMemset(f, 0, nf) != hipSuccess || hipMemcpy(f, r->q_tile_flag, (size_t)r->Mpad / 32, hipMemcpyHostToDevice) != hipSuccess) msg = "gemm_run: upload failed";
-        g.q_tile_flag = f;
-    }
-    if (r->ws_bytes) { g.ws = (float*)bufs.get(r->ws_bytes); g.ws_bytes = r->ws_bytes; if (!g.ws) msg = "gemm_run: alloc failed"; }
-    if (msg) return fail(msg, -1);
-    // outputs: [guard | bytes | guard], all prefilled
-    struct Guarded { unsigned char* base = nullptr; size_t bytes = 0; };
-    Guarded outs[4];
-    const int fillb = r->fill & 255;
-    auto guarded = [&](Guarded& o, size_t bytes) {
-        o.bytes = bytes;
-        o.base = (unsigned char*)bufs.get(bytes + 2 * RUN_GUARD);
-        return o.base && hipMemsetAsync(o.base, fillb, bytes + 2 * RUN_GUARD, st) == hipSuccess;
-    };
-    for (int i = 0; i < 3; ++i) {
-        const size_t need = gemm_run_out_bytes(*r, dtype, i);
-        if (need > r->out_bytes[i]) return fail("gemm_run: out_bytes is smaller than the output this launch writes", -1);
-        if (!guarded(outs[i], std::max<size_t>(need, 16))) return fail("gemm_run: alloc failed", -1);
-    }
-    const size_t lp_bytes = (size_t)r->Mpad * (size_t)(r->N / 64) * 8;
-    if (r->want_ln_part) { if (!guarded(outs[3], std::max<size_t>(lp_bytes, 16))) return fail("gemm_run: alloc failed", -1); g.ln_part = (float2*)(outs[3].base + RUN_GUARD); }
-    if (r->epi == EPI_QKV || r->epi == EPI_QKVR) { g.Qh = outs[0].base + RUN_GUARD; g.Kh = outs[1].base + RUN_GUARD; g.Vt = outs[2].base + RUN_GUARD; }
-    else g.C = outs[0].base + RUN_GUARD;
-    unsigned* sat = (unsigned*)bufs.get(8);
-    if (!sat || hipMemsetAsync(sat, 0, 8, st) != hipSuccess) return fail("gemm_run: alloc failed", -1);
-    if (mx) g.gx_sat = sat;
-    // the one launcher call
-    switch (kern) {
-        case GLC_GEMM_RUN_128: msg = glc_launch_gemm(st, dtype, r->epi, g); break;
-        case GLC_GEMM_RUN_256S: msg = glc_launch_gemm256s(st, dtype, r->epi, g); break;
-        case GLC_GEMM_RUN_GS: msg = glc_launch_gemm256s_gs(st, r->epi, g); break;
-        case GLC_GEMM_RUN_MX: msg = glc_launch_gemm256x(st, r->epi, g); break;
-        default: msg = glc_launch_gemm_auto(st, dtype, r->epi, g); break;
-    }
-    if (msg) return fail(msg, -2);
-    hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipStreamSynchronize(st);
-    if (he != hipSuccess) { set_err(std::string("gemm_run: ") + hipGetErrorString(he)); return -1; }
-    auto back = [&](void* h, const void* d, size_t bytes) { return !h || !bytes || hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
-    bool ok = true;
-    for (int i = 0; i < 3; ++i) ok = ok && back(r->out[i], outs[i].base + RUN_GUARD, gemm_run_out_bytes(*r, dtype, i));
-    if (r->want_ln_part) ok = ok && back(r->ln_part, outs[3].base + RUN_GUARD, lp_bytes);
-    ok = ok && back(r->A_img, g.A, nA * es) && back(r->W_img, g.W, nW * es) && (!g.W2 || back(r->W2_img, g.W2, nW * es)) &&
-         (!g.resid || back(r->resid_img, g.resid, nC * (gs && r->gs_resid_plain ? 4 : es))) && back(r->sat, sat, 8);
-    std::vector<unsigned char> gd(RUN_GUARD);
-    r->guards_ok = 1;
-    r->cus = glc_device_cus();
-    for (int i = 0; i < 4 && ok; ++i) {
-        if (!outs[i].base) continue;
-        for (int side = 0; side < 2 && ok; ++side) {
-            ok = back(gd.data(), outs[i].base + (side ? RUN_GUARD + outs[i].bytes : 0), RUN_GUARD);
-            for (size_t k = 0; k < RUN_GUARD && ok; ++k) if (gd[k] != (unsigned char)fillb) { r->guards_ok = 0; break; }
-        }
-    }
-    if (!ok) { set_err("gemm_run: readback failed"); return -1; }
-    return 0;
-}
-
-int glc_debug_ln_stats_run(glc_engine* e, const float* part, int nparts, int M, float eps, int rms, float* stats) {
-    if (!e || !part || !stats || M <= 0 || nparts <= 0 || M > (1 << 20) || nparts > 1024) { set_err("ln_stats_run: bad args"); return -1; }
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHK(hipSetDevice(e->device), -1);
-    RunBufs bufs;
-    const float2* dp = (const float2*)bufs.up(part, (size_t)M * nparts * 8);
-    float2* ds = (float2*)bufs.get((size_t)M * 8);
-    if (!dp || !ds) { set_err("ln_stats_run: alloc failed"); return -1; }
-    KCHK(glc_launch_ln_stats(e->stream, dp, nparts, ds, M, nparts * 64, eps, rms), -2);
-    HIPCHK(hipStreamSynchronize(e->stream), -1);
-    HIPCHK(hipMemcpy(stats, ds, (size_t)M * 8, hipMemcpyDeviceToHost), -1);
-    return 0;
-}
-
-/* Developer microbenchmark: re-run the band attention kernel `iters` times on the Q/K/V^T that the last forward left in the
- * workspace (layer-0 position tables), HIP-event timed.  checksum[0..1] = sum and sum of squares of the context output;
- * variant is passed through to the kernel; stamps != 0 adds one launch of the s_memtime-instrumented build and prints
- * the per-tile segment cycles.  Returns ms per launch or < 0. */
-float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, double* checksum) {
-    if (!e || iters <= 0 || (e->dtype == GLC_F32 && !e->attn_split) || e->lastB <= 0 || e->cfg.backbone != GLC_BACKBONE_DEBERTA) {
-        set_err("attn_bench: needs a DeBERTa engine (16-bit, or fp32 with split-f16 attention) and a previous forward"); return -1.f;
-    }
-    constexpr int MX_DEV = 256 | 512 | 4096 | 16384 | 65536 | 131072 | 262144 | 1048576;     // the MX kernel's timing-only and measurement builds
-    if (variant & ~(255 | 1024 | 2048 | MX_DEV)) { set_err("attn_bench: no attention kernel takes these variant bits"); return -1.f; }
-#ifndef GLC_DEVELOPER
-    if (stamps || (variant & MX_DEV)) { set_err("attn_bench: stamped and timing-only builds (wrong results) exist in developer builds only (make DEV=1)"); return -1.f; }
-#endif
-    std::lock_guard<std::mutex> lk(e->mu);
-    HIPCHK(hipSetDevice(e->device), -1.f);
-    const int B = e->lastB, Sp = e->lastSp, H = e->cfg.hidden, nh = e->cfg.heads;
-    const LayerW& w = e->layers[0];
-    const bool sp = e->dtype == GLC_F32;
-    AttnArgs a{e->Qh, e->Kh, e->Vt, sp ? w.PKs : w.PK, sp ? w.PQs : w.PQ, e->dtabs[Sp], e->kbias, e->klen, e->kfirst, e->CTX, B, nh, Sp, H, e->P};
-    a.rsat_pos = e->dsat[Sp].first; a.rsat_neg = e->dsat[Sp].second; a.variant = variant & 123; a.otab = e->otabs[Sp]; a.mtab = e->mtabs.count(Sp) ? e->mtabs[Sp] : nullptr; a.split = sp;    // bits 0-1: per-wave kernel diagnostics; bit 3: wg kernel without the K/V ring; bits 4 / 5: wg kernel with / without the half-tile stagger
-    hipStream_t st = e->stream;
-    const bool wg = (variant & 4) != 0;                       // bit 2: the workgroup-shared kernel (attention_wg.hip)
-    const bool mxk = (variant & 128) != 0;                    // bit 7: the MX-tile kernel (attention_mx.hip) on the MX tiles the last (MX) forward left; bits 8 / 9: its timing-only builds
-    if (mxk) {
-        if (!(sp && e->last_mx && e->mx_attn && w.PKm && w.PQm)) { set_err("attn_bench: the MX kernel needs a previous forward of the MX pipeline with MX attention"); return -1.f; }
-        a.PK = w.PKm; a.PQ = w.PQm; a.ctx_gs = 2; a.variant = variant & (1024 | 2048 | MX_DEV);
-    }
-    auto launch = [&]() -> const char* { return mxk ? glc_launch_attention_mx(st, a) : wg ? glc_launch_attention_wg(st, e->dtype, a) : glc_launch_attention(st, e->dtype, 2, a); };
-    for (int i = 0; i < 2; ++i) KCHK(launch(), -1.f);
-    HIPCHK(hipEventRecord(e->t0, st), -1.f);
-    for (int i = 0; i < iters; ++i) launch();
-    HIPCHK(hipEventRecord(e->t1, st), -1.f);
-    HIPCHK(hipEventSynchronize(e->t1), -1.f);
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e->t0, e->t1), -1.f);
-    if (checksum) {
-        const size_t n = (size_t)B * Sp * H;
-        float* tmp = nullptr;
-        HIPCHK(hipMalloc((void**)&tmp, n * sizeof(float)), -1.f);
-        std::vector<float> h(n);
-        const char* m = mxk ? nullptr : glc_launch_to_f32(st, e->dtype, e->CTX, tmp, n);
-        if (mxk) { HIPCHK(hipMemsetAsync(tmp, 0, n * sizeof(float), st), -1.f); }        // (GX rows: no checksum)
-        hipError_t r = m ? hipErrorUnknown : hipMemcpyAsync(h.data(), tmp, n * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (r == hipSuccess) r = hipStreamSynchronize(st);
-        (void)hipFree(tmp);
-        if (r != hipSuccess) { set_err("attn_bench: readback failed"); return -1.f; }
-        double s1 = 0, s2 = 0;
-        for (size_t i = 0; i < n; ++i) { s1 += h[i]; s2 += (double)h[i] * h[i]; }
-        checksum[0] = s1; checksum[1] = s2;
-    }
-    if (stamps && wg && sp && !(variant & 121)) {       // the split-f16 workgroup kernel, stamped build: 64 workgroups x 8 waves x 8 counters
-        unsigned long long* dbuf = nullptr;
-        const size_t ns = 64 * 8 * 8;
-        if (hipMalloc((void**)&dbuf, ns * sizeof(unsigned long long)) == hipSuccess) {
-            (void)hipMemsetAsync(dbuf, 0, ns * sizeof(unsigned long long), st);
-            AttnArgs as = a; as.stamps = dbuf;
-            const char* m = glc_launch_attention_wg(st, e->dtype, as);
-            (void)hipStreamSynchronize(st);
-            std::vector<unsigned long long> hs(ns);
-            if (!m && hipMemcpy(hs.data(), dbuf, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                double s[8] = {0};
-                for (size_t i = 0; i < 64 * 8; ++i) for (int k = 0; k < 8; ++k) s[k] += (double)hs[i * 8 + k];
-                const double nt = s[7] > 0 ? s[7] : 1;
-                fprintf(stderr, "[attn_wg stamps] per band tile per wave (s_memtime ticks), %.0f tiles: request wait %.0f | K+gather+p2c/S issue %.0f | barrier X %.0f | "
-                                "image stores + barrier Y %.0f | DMA, image gather, c2p issue %.0f | softmax + P.V + c2p store %.0f | total %.0f | s_memtime clock %.0f MHz\n",
-                        nt, s[0] / nt, s[1] / nt, s[2] / nt, s[3] / nt, s[4] / nt, s[5] / nt, (s[0] + s[1] + s[2] + s[3] + s[4] + s[5]) / nt, s[6] / (64 * 8) / 10.0);
-            } else if (m) fprintf(stderr, "[attn_wg stamps] %s\n", m);
-            (void)hipFree(dbuf);
-        }
-    }
-    if (stamps && mxk) {       // the MX-tile kernel, stamped build: 64 workgroups x 8 waves x 10 counters
-        unsigned long long* dbuf = nullptr;
-        const size_t ns = 64 * 8 * 10;
-        if (hipMalloc((void**)&dbuf, ns * sizeof(unsigned long long)) == hipSuccess) {
-            (void)hipMemsetAsync(dbuf, 0, ns * sizeof(unsigned long long), st);
-            AttnArgs as = a; as.stamps = dbuf;
-            const char* m = glc_launch_attention_mx(st, as);
-            (void)hipStreamSynchronize(st);
-            std::vector<unsigned long long> hs(ns);
-            if (!m && hipMemcpy(hs.data(), dbuf, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                double s[10] = {0};
-                for (size_t i = 0; i < 64 * 8; ++i) for (int k = 0; k < 10; ++k) s[k] += (double)hs[i * 10 + k];
-                const double nt = s[9] > 0 ? s[9] : 1;
-                double tot = 0;
-                for (int k = 0; k < 8; ++k) tot += s[k];
-                fprintf(stderr, "[attn_mx stamps] per band tile per wave (s_memtime ticks), %.0f tiles: request wait %.0f | K + c2p gather + p2c/S issue %.0f | row requests %.0f | "
-                                "barrier X %.0f | image stores + barrier Y %.0f | DMA + image gather %.0f | c2p issue + softmax + P.V %.0f | c2p store %.0f | total %.0f | s_memtime clock %.0f MHz\n",
-                        nt, s[0] / nt, s[1] / nt, s[2] / nt, s[3] / nt, s[4] / nt, s[5] / nt, s[6] / nt, s[7] / nt, tot / nt, s[8] / (64 * 8) / 10.0);
-            } else if (m) fprintf(stderr, "[attn_mx stamps] %s\n", m);
-            (void)hipFree(dbuf);
-        }
-    }
-    if (stamps && !wg && !sp) {
-        unsigned long long* dbuf = nullptr;
-        const size_t ns = 64 * 4 * 8;
-        if (hipMalloc((void**)&dbuf, ns * sizeof(unsigned long long)) == hipSuccess) {
-            (void)hipMemsetAsync(dbuf, 0, ns * sizeof(unsigned long long), st);
-            AttnArgs as = a; as.stamps = dbuf;
-            glc_launch_attention(st, e->dtype, 2, as);
-            (void)hipStreamSynchronize(st);
-            std::vector<unsigned long long> hs(ns);
-            if (hipMemcpy(hs.data(), dbuf, ns * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess) {
-                double s[8] = {0};
-                for (size_t i = 0; i < 64 * 4; ++i) for (int k = 0; k < 8; ++k) s[k] += (double)hs[i * 8 + k];
-                const double nt = s[7] > 0 ? s[7] : 1;
-                fprintf(stderr, "[attn stamps] per band tile per wave (s_memtime ticks), %0.f tiles: mfma_qk_p2c+stores %.0f | lds_sync %.0f | gather %.0f | "
-                                "max+xchg %.0f | exp+sum %.0f | cvt+pv %.0f | c2p_next %.0f | total %.0f\n",
-                        nt, s[0] / nt, s[1] / nt, s[2] / nt, s[3] / nt, s[4] / nt, s[5] / nt, s[6] / nt,
-                        (s[0] + s[1] + s[2] + s[3] + s[4] + s[5] + s[6]) / nt);
-            }
-            (void)hipFree(dbuf);
-        }
-    }
-    return t / iters;
-}
-
-/* 1: this library was built with make DEV=1 (developer kernels, stamps and the GLC_* environment switches compiled in); 0: the product library. */
-int glc_debug_is_developer_build(void) {
-#ifdef GLC_DEVELOPER
-    return 1;
-#else
-    return 0;
-#endif
 }
 
 const glc_model_config* glc_engine_config(const glc_engine* e) { return e ? &e->cfg : nullptr; }

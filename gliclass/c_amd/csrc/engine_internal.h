@@ -1,0 +1,137 @@
+// What engine.hip (load, workspace, forwards) and engine_debug.hip (developer entries that allocate their own buffers or launch kernels
+// outside a forward) share: the engine itself, the error setter behind glc_last_error() and the two check macros.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <map>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../../include/gliclass_hip.h"
+#include "glc_kernels.h"
+
+void glc_set_err(const std::string& s);      // engine.hip: the calling thread's glc_last_error() text
+
+#define HIPCHK(expr, ret)                                                                          \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) {                                                                    \
+            glc_set_err(std::string(#expr) + ": " + hipGetErrorString(_e));                        \
+            return ret;                                                                            \
+        }                                                                                          \
+    } while (0)
+#define KCHK(expr, ret)                                                                            \
+    do {                                                                                           \
+        const char* _m = (expr);                                                                   \
+        if (_m) { glc_set_err(_m); return ret; }                                                   \
+    } while (0)
+
+inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+inline size_t esize(int dtype) { return dtype == GLC_F32 ? 4 : 2; }
+
+enum { PC_SCAN = 0, PC_EMBED, PC_QKV, PC_ATTN, PC_ATTN_OUT, PC_LN, PC_FFN1, PC_FFN2, PC_HEAD, PC_LAST, PC_N };
+const char* const kProfNames[PC_N] = {"scan_rows", "embed_ln", "gemm_qkv", "attention", "gemm_attn_out", "layernorm",
+                                      "gemm_ffn1_gelu", "gemm_ffn2", "head", "last_layer_pruned"};
+
+struct DecLayerW {                     // decoder-style backbone (decoder.hip)
+    void *Wqkv = nullptr, *Wo = nullptr, *Wgu = nullptr, *Wd = nullptr;       // T: [(nq+2nkv)d, H], [H, nq d], [2I, H] (gate rows | up rows), [H, I]
+    float *bqkv = nullptr, *ln1 = nullptr, *ln2 = nullptr;                    // f32
+    void *Wqkvf = nullptr, *Wguf = nullptr;                                   // fp32 mode, RMSNorm folded into the GEMMs: Wqkv diag(ln1), Wgu diag(ln2), group-split
+    void *Wqkvf_x = nullptr, *Wo_x = nullptr, *Wguf_x = nullptr, *Wd_x = nullptr;   // MX pipeline: the same four as GX rows + their fp8 exponents
+    int ws_qkvf = 0, ws_o = 0, ws_guf = 0, ws_d = 0;
+    float* bqkv_p = nullptr;            // bqkv in the row order of a Wqkvf_x built for the RoPE epilogue (glc_rope_perm128), else null
+};
+
+struct LayerW {
+    void *Wqkv = nullptr, *Wo = nullptr, *W1 = nullptr, *W2 = nullptr;       // T
+    float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;       // f32
+    float *ln1g = nullptr, *ln1b = nullptr, *ln2g = nullptr, *ln2b = nullptr; // f32
+    void *PK = nullptr, *PQ = nullptr;                                        // T [nh, P, 64]
+    void *PKs = nullptr, *PQs = nullptr;                                      // fp32 mode: the same tables as split-f16 units (band kernel, AttnArgs::split)
+    // LayerNorm folded into the group-split GEMMs (GemmArgs::a_stats): W1 . diag(ln1 gamma), Wqkv . diag(previous layer's ln2 gamma)
+    // as group-split rows, their row sums c and the folded biases d = W beta + b
+    void *W1f = nullptr, *Wqkvf = nullptr;
+    float *c1 = nullptr, *d1 = nullptr, *cq = nullptr, *dq = nullptr;
+    // MX pipeline (glc_engine::mx): the projection weights once more as GX rows (glc_common.h) with their fp8 exponents
+    void *PKm = nullptr, *PQm = nullptr;                                     // the position tables as MX tiles (attention_mx.hip)
+    void *Wqkv_x = nullptr, *Wqkvf_x = nullptr, *Wo_x = nullptr, *W1f_x = nullptr, *W2_x = nullptr;
+    int ws_qkv = 0, ws_qkvf = 0, ws_o = 0, ws_1f = 0, ws_2 = 0;
+};
+
+struct glc_engine {
+    glc_model_config cfg{};
+    int dtype = GLC_F32, device = 0, attn_impl = 0;
+    bool prune_last = true;         // last layer only on the rows the head reads (exact)
+    bool w_presplit = false;        // weights of the split-f16 fp32 GEMMs are split once at load (encoder layers in fp32 mode; head projectors in every mode)
+    bool dec_split = false;         // decoder backbone, fp32 mode: RoPE/layout pass writes split-f16 units, grouped-query attention on three-MFMA products
+    bool attn_split = false;        // fp32 mode: band attention on split-f16 operands (three f16 MFMAs per product); GLICLASS_F32_ATTN=native turns it off
+    bool mx_built = false, mx = false;   // MX cross-term projections (gemm256x.hip) on GX rows: allowed for this engine / pipeline selected (GLICLASS_MX, glc_debug_set_mx)
+    bool mx_ready = false;               // ... and the GX copies of the projection weights exist: built from the split-f16 copies by the first forward that takes the pipeline
+    size_t mx_bytes = 0;                 // their size (glc_debug_mx_weight_bytes)
+    bool last_mx = false;                // the last forward ran the MX pipeline
+    bool last_mx_attn = false;           // ... and its attention ran on MX tiles (attention_mx.hip)
+    bool dec_rope_epi = true;            // decoder MX pipeline: RoPE + MX tiles as the QKV projection's epilogue (gemm256x EPI_QKVR); GLC_DEC_ROPE_EPI=0: the separate pass
+    bool mx_attn = true;                 // MX pipeline: attention on MX tiles (attention_mx.hip); false: split-f16 units (GLC_MX_ATTN=0, glc_debug_set_mx_attention)
+    int debug_stop = -1;                 // developer: leave run_forward after stage (10 * layer + k), k = 0 QKV, 1 attention, 2 attn-out, 3 FFN1, 4 FFN2 (+ LayerNorm): workspace inspection
+    int prec_mask = 0;              // precision-budget switches (PM_* of glc_kernels.h; glc_debug_set_precision_mask): operands rounded to f16 in the group-split pipeline
+    int gs_mode = 1;                // fp32 mode, group-split activations + 256-tile LDS-DMA GEMMs: 0 off, 1 auto (large shapes), 2 whenever the shapes allow (tests)
+    bool last_gs = false;           // the last forward ran the group-split pipeline
+    bool ln_fused = true;           // group-split pipeline: LayerNorm folded into the GEMMs around it (GLC_LNF=0: separate LayerNorm kernels)
+    bool last_lnf = false;          // the last forward ran with LayerNorm / RMSNorm folded into its GEMMs
+    float2 *statsA = nullptr, *statsB = nullptr, *ln_part = nullptr;     // (mean, rstd) per row of X / H1 when they hold raw sums; the producers' partials
+    int max_buckets = 4;            // host-buffer forward: split a ragged batch into <= this many length groups (1 = off)
+    int last_groups = 1;            // groups the last host-buffer forward ran as
+    int range_retries = 0;          // host-buffer forwards repeated with the norms unfused because the folded one came out non-finite
+    // fp8 range guard of the MX pipeline (glc_common.h gx_range_note): device counter of activation elements beyond the e4m3 range, its value after the
+    // last checked forward, a pinned host slot for the device-resident path; forwards repeated on the split-f16 kernels because they counted
+    // any; consecutive such forwards (the model has outlier channels: after kFp8Sticky of them the engine leaves the MX pipeline for good)
+    unsigned* d_gxsat = nullptr; unsigned gxsat_seen[2] = {0, 0}; unsigned* h_gxsat = nullptr;      // two words: [0] activation rows (GX images, exponent act_sc), [1] Q / K / V MX tiles (exponent 0)
+    int fp8_retries = 0, fp8_streak = 0; bool fp8_sticky_off = false, fp8_device_pending = false;
+    int device_invalid = 0;                    // a device-resident forward since the last glc_engine_sync left the fp8 range (1: rows only, 2: tiles): its logits are not valid
+    // Activation exponent of the MX pipeline's GX rows (hi8 = e4m3(x 2^act_sc), glc_common.h): 0 until a forward leaves the e4m3 range (|x| > 448);
+    // the guard's FIRST answer is then kActScLow = -5 for this engine (rows hold |x| up to 14336, elements below 0.5 keep fewer hi8 bits — their
+    // cross terms are 2^-16 of a unit product either way) and the forward is repeated on the MX pipeline; only what still leaves the range
+    // (or an MX tile of the attention: Q, K, V, P keep exponent 0) goes to the split-f16 kernels.
+    int act_sc = 0;
+    float* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;     // fp32 partial tiles of the split-K GEMM path (small M)
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    std::vector<void*> allocs;      // everything freed at destroy
+    // weights
+    void* emb = nullptr; float *eln_g = nullptr, *eln_b = nullptr;
+    std::vector<LayerW> layers;
+    std::vector<DecLayerW> dlayers; float* final_norm = nullptr;      // decoder backbone; ModernBERT: Wgu = Wi, Wd = mlp.Wo, ln1 / ln2 = attn_norm / mlp_norm
+    float* zero_bias = nullptr;                                       // ModernBERT: [H] zeros, the beta of its bias-free LayerNorms
+    std::map<std::pair<int, float>, float*> ropes;                    // (Sp, theta) -> [Sp][d/2][cos,sin]
+    void *QKV = nullptr, *GU = nullptr, *X2 = nullptr;                // decoder workspace: fused QKV rows, [gate|up] rows, second residual buffer
+    bool fused_swiglu = false;                                        // Wgu rows interleaved 16 gate / 16 up: SwiGLU runs in the GEMM epilogue
+    float* headw[8] = {nullptr};
+    float* scw[8] = {nullptr};           // the scorer's own tensors (weighted-dot: 8, mlp: 6, simple: none), fp32
+    float* scorer_ws = nullptr;          // its row buffers
+    int P = 0;
+    // workspace
+    int capM = 0, capB = 0, capIds = 0, capC = 0, capHeadRows = 0, capSel = 0, capGU = 0;
+    void *Xs = nullptr, *Qs = nullptr, *CTXs = nullptr, *T1s = nullptr, *H1s = nullptr, *FFs = nullptr;   // compact rows of the pruned last layer
+    int *sel_b = nullptr, *sel_q = nullptr;
+    unsigned char* tile_flag = nullptr; size_t capFlag = 0;
+    void *X = nullptr, *Qh = nullptr, *Kh = nullptr, *Vt = nullptr, *CTX = nullptr, *T1 = nullptr, *H1 = nullptr, *FF = nullptr;
+    float* kbias = nullptr; int *klen = nullptr, *kfirst = nullptr, *cls_pos = nullptr, *cls_cnt = nullptr;
+    int64_t *d_ids = nullptr, *d_mask = nullptr;
+    float *Gt = nullptr, *G1t = nullptr, *G2t = nullptr, *d_logits = nullptr;   // head rows: [text | class] groups, 128-aligned
+    std::map<int, int32_t*> dtabs;
+    std::map<int, int2*> mtabs;                // Sp -> the MX band kernel's ready-made row offsets (round 6; fp32 mode only): glc_kernels.h AttnArgs::mtab
+    std::map<int, int2*> otabs;                // Sp -> byte offsets of the PQ / PK rows per relative distance (band kernel, 16-bit)
+    std::map<int, std::pair<int, int>> dsat;   // Sp -> (rsat_pos, rsat_neg)
+    // last forward
+    int lastB = 0, lastS = 0, lastSp = 0;
+    // debug
+    bool keep_hidden = false; void* hidden_dump = nullptr; size_t hidden_cap = 0;
+    // timing / profile
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    bool profile = false;
+    struct Ev { hipEvent_t a, b; int cls; };
+    std::vector<Ev> evs; size_t ev_used = 0;
+    float prof_ms[PC_N] = {0}; int prof_n[PC_N] = {0};
+};

@@ -180,7 +180,7 @@ int glc_debug_last_forward_mx(const glc_engine* e);
 int glc_debug_last_forward_mx_attention(const glc_engine* e);   /* 1: the last forward's attention ran on MX tiles (two MFMA times per product) */
 int glc_debug_set_mx_attention(glc_engine* e, int on);                 /* MX pipeline: attention on MX tiles (default) / on split-f16 units */
 long long glc_debug_mx_weight_bytes(const glc_engine* e);  /* bytes of the GX weight copies (0 until a forward has taken the MX pipeline: they are built then) */
-/* Developer: stop forwards after a stage and read workspace rows decoded to fp32 (engine.hip). */
+/* Developer: stop forwards after a stage (engine.hip) and read workspace rows decoded to fp32 (engine_debug.hip). */
 int glc_debug_set_stop(glc_engine* e, int stage);
 int glc_debug_read_workspace(glc_engine* e, int which, int rows, float* out);
 /* Group-split pipeline: LayerNorm folded into the GEMMs around it (1, default: the producer writes raw rows + row statistics, the consumer
@@ -211,9 +211,8 @@ void glc_delta_table(int S, int bucket_size, int max_position, int32_t* out);
 
 /* Developer microbenchmark of one GEMM shape (16-bit engines): ms per launch, <0 on error. */
 float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iters, int which);
-/* Developer check: MX cross-term GEMM against the split-f16 GEMM on the same random operands (engine.hip). */
-int glc_debug_gemm_mx_check(glc_engine* e, int M, int N, int K, float a_amp, float w_amp, int mode, double* out);
-/* Kernel-level tests (tests/test_gpu_gemm_kernels.py): ONE launcher call of one GEMM kernel on operands the caller chose.
+/* Kernel-level tests (tests/test_gpu_gemm_kernels.py; tests/test_gpu_mx.py: the MX cross-term GEMM against the split-f16 GEMM on the same
+ * operands, two calls per case): ONE launcher call of one GEMM kernel on operands the caller chose.
  * The host fp32 operands are encoded with the library's own converters (glc_launch_convert / _presplit / _to_gx / _gs_to_gx), the launcher
  * runs once, and the RAW BYTES of every output, of ln_part, of the encoded operand images and the two words of the fp8 range counter come
  * back; decoding them is the caller's business (tests/gemm_ref.py: a second reading of the formats).  Every output sits between two guard
@@ -240,7 +239,7 @@ typedef struct glc_gemm_run {
     int32_t fill;                                      /* byte the outputs, ln_part and the guards are prefilled with */
     uint64_t ws_bytes;                                 /* split-K workspace of the 128-tile kernel; 0 = none */
     /* ---- out (host buffers of the caller; a null pointer skips that copy) ---- */
-    void* out[3]; uint64_t out_bytes[3];               /* C, or Qh / Kh / Vt: capacity, at least the bytes of that output (engine.hip gemm_run_out_bytes) */
+    void* out[3]; uint64_t out_bytes[3];               /* C, or Qh / Kh / Vt: capacity, at least the bytes of that output (engine_debug.hip gemm_run_out_bytes) */
     void* ln_part;                                     /* Mpad * (N / 64) * 8 bytes */
     void *A_img, *W_img, *W2_img, *resid_img;          /* the encoded operands: element bytes (2, or 4 for fp32 / GS / GX) x count */
     uint32_t sat[2];                                   /* the fp8 range counter after the launch */
@@ -250,7 +249,7 @@ typedef struct glc_gemm_run {
 int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r);
 /* glc_launch_ln_stats on host partials part [M][nparts] (sum, M2) -> stats [M] (mean, rstd) pairs; rms: (0, 1 / sqrt(E[x^2] + eps)) */
 int glc_debug_ln_stats_run(glc_engine* e, const float* part, int nparts, int M, float eps, int rms, float* stats);
-/* Developer microbenchmark of the band attention kernel on the workspace of the last forward (see engine.hip). */
+/* Developer microbenchmark of the band attention kernel on the workspace of the last forward (see engine_debug.hip). */
 float glc_debug_attn_bench(glc_engine* e, int iters, int variant, int stamps, double* checksum);
 int glc_debug_is_developer_build(void);                  /* 1: built with make DEV=1 (developer kernels, stamps, GLC_* switches); 0: the product library */
 

@@ -1,14 +1,18 @@
 """GPU (-m gpu): the MX cross-term GEMM (gemm256x.hip: a_hi*w_hi in f16 MFMAs + both cross terms in one block-scaled fp8 MFMA, GX rows)
 against the split-f16 GEMM (gemm256s.hip, three f16 MFMAs per product, group-split rows) on the same random fp32 operands — every
-epilogue path the pipeline uses, through the C-ABI's developer entry glc_debug_gemm_mx_check.  The product error bound of the MX
-arithmetic is ~2^-15 relative (cross terms to ~4 bits); measured 1e-5 relative rms.  The whole-forward error of the MX pipeline is
-asserted in test_gpu_parity.py (forced pipeline, mini / small) and test_gpu_fullsize.py (c3, three seeds; c4's shard).
+epilogue path the pipeline uses: two glc_debug_gemm_run calls per case (tests/gemm_run.py), their raw output bytes decoded by the numpy
+codecs of tests/gemm_ref.py.  The product error bound of the MX arithmetic is ~2^-15 relative (cross terms to ~4 bits); measured 1e-5
+relative rms.  The whole-forward error of the MX pipeline is asserted in test_gpu_parity.py (forced pipeline, mini / small) and
+test_gpu_fullsize.py (c3, three seeds; c4's shard).
 Each kernel on its own against float64 references, with derived per-element bounds: tests/test_gpu_gemm_kernels.py."""
 import ctypes as C
 import os
 
 import numpy as np
 import pytest
+
+import gemm_ref as R
+from gemm_run import run
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,12 +21,62 @@ MODES = {0: "bias, plain fp32 out", 1: "GELU + LayerNorm fold, row out", 2: "res
          3: "residual, plain fp32 out", 4: "QKV + LayerNorm fold, split-f16 units"}
 
 
+def _mx_and_split_outputs(eng, mode, M, N, K, a_amp, w_amp):
+    """One case on both kernels -> (GS values, MX values, GS ln_part, MX ln_part), the values decoded to float64 in storage order."""
+    rng = np.random.default_rng([mode, M, N, K])
+    U = lambda *shape: rng.uniform(-1.0, 1.0, shape).astype(np.float32)
+    A, W, resid = a_amp * U(M, K), w_amp * U(N, K), a_amp * U(M, N)
+    bias, ln_c, gamma, beta = 0.1 * U(N), 0.05 * U(N), 1.0 + 0.3 * U(N), 0.2 * U(N)
+    stats = np.stack([0.1 * U(M) * a_amp, (0.5 + 0.4 * U(M)) / a_amp], 1).astype(np.float32)
+    epi, o = R.EPI_BIAS, dict(bias=bias)
+    if mode == 0:
+        o.update(gs_c_plain=1)
+    elif mode == 1:
+        epi = R.EPI_GELU; o.update(a_stats=stats, ln_c=ln_c)
+    elif mode == 2:
+        epi = R.EPI_RESID; o.update(resid=resid, r_stats=stats, r_gamma=gamma, r_beta=beta, want_ln_part=1)
+    elif mode == 3:
+        epi = R.EPI_RESID; o.update(resid=resid)
+    else:
+        H = N // 3
+        epi = R.EPI_QKV; o.update(a_stats=stats, ln_c=ln_c, H=H, nh=H // 64, Sp=256, Mvalid=M, qkv_split=1)
+    vals, parts = [], []
+    for kernel, extra in ((R.KGS, {}), (R.KMX, dict(mx_ws=R.gx_weight_exponent(w_amp)))):
+        res = run(eng, kernel, epi, A, W, **o, **extra)
+        assert res["rc"] == 0, res["err"]
+        assert res["guards_ok"] == 1, "a guard region was written"
+        if mode == 4:          # Q, K, V^T as [8 hi | 8 lo] f16 units
+            qkv = R.qkv_decode([b.tobytes() for b in res["out"]], "f16", True, M // 256, N // 3 // 64, 256)
+            v = np.concatenate([(hi.astype(np.float64) + lo).reshape(-1) for hi, lo in qkv])
+        elif mode in (1, 2):   # GS rows hi + lo; GX rows hi + lo8 2^-SHIFT (activation exponent 0)
+            if kernel == R.KGS:
+                hi, lo = R.gs_decode(res["out"][0], M, N)
+                v = hi.astype(np.float64) + lo
+            else:
+                # The activation split does not clamp (glc_common.h gx_split8): beyond the e4m3 range an fp8 part is the NaN code and the range
+                # guard counts the element, so that the engine repeats such a forward.  The a_amp = 50 case of mode 2 gets there (|x| up to
+                # ~700; from 512 on a lo part can exceed 464 2^-11).  Such codes are read as the saturated +-448, close to how the removed C
+                # check read them (+-480, it had no NaN case) — and only where the guard did count.
+                raw = res["out"][0].reshape(M, N // 32, 128).copy()
+                f8 = raw[:, :, 64:]                                        # the 64 fp8 bytes behind the 32 f16 hi halves of every group
+                nan = (f8 & 0x7F) == 0x7F
+                assert not nan.any() or res["sat"][0] > 0, "NaN codes in GX rows the range guard did not count"
+                f8[nan] -= 1
+                hi, lo8, _ = R.gx_decode(raw.reshape(-1), M, N, 0)
+                v = hi.astype(np.float64) + lo8 * 2.0 ** -R.GX_SHIFT
+        else:
+            v = np.frombuffer(res["out"][0].tobytes(), np.float32).astype(np.float64)
+        assert v.size == M * N
+        vals.append(v.reshape(-1))
+        parts.append(res["ln_part"].astype(np.float64))
+    return vals[0], vals[1], parts[0], parts[1]
+
+
 @pytest.mark.parametrize("mode", sorted(MODES))
 def test_mx_gemm_every_epilogue_vs_split_gemm(mode, weights_for):
     from gliclass.c_amd.engine import Engine
     cfg, w = weights_for("tiny")
     eng = Engine(cfg, w, dtype="f16")
-    out = (C.c_double * 5)()
     try:
         # (the last three shapes have N K >= 768 x 3072: bias / GELU / residual launches take the one-wave-per-SIMD 128 x 128 tile there (round 6) — K = 32 is its
         #  shortest loop: prologue + a peeled tail only — the others the 8-wave tile)
@@ -30,13 +84,17 @@ def test_mx_gemm_every_epilogue_vs_split_gemm(mode, weights_for):
                                         (512, 3072, 768, 1.0, 0.05), (512, 1536, 1536, 2.0, 0.05), (256, 73728, 32, 1.0, 0.05), (256, 36864, 64, 1.0, 0.05)):
             if mode == 4:
                 N = 768                      # N = 3 H, H = 256: a tile never straddles Q | K | V
-            rc = eng.L.glc_debug_gemm_mx_check(eng.h, M, N, K, a_amp, w_amp, mode, out)
-            assert rc == 0, eng.L.glc_last_error().decode()
-            max_d, max_ref, rms_d, rms_ref, part_d = (out[i] for i in range(5))
+            gs, mx, part_gs, part_mx = _mx_and_split_outputs(eng, mode, M, N, K, a_amp, w_amp)
+            d = mx - gs
+            max_d, max_ref, rms_d, rms_ref = float(np.abs(d).max()), float(np.abs(gs).max()), float(np.sqrt(np.mean(d * d))), float(np.sqrt(np.mean(gs * gs)))
+            print(f"[mx vs split] mode {mode} M={M} N={N} K={K}: rms ratio {rms_d / rms_ref:.3e}, max ratio {max_d / max_ref:.3e}")
             assert np.isfinite(max_d) and rms_ref > 0
             assert rms_d <= 4e-5 * rms_ref, (MODES[mode], M, N, K, rms_d / rms_ref)       # ~2^-15 per product; a layout error is O(1)
             assert max_d <= 4e-4 * max_ref, (MODES[mode], M, N, K, max_d / max_ref)
             if mode == 2:
+                dp = np.abs(part_mx - part_gs)
+                part_d = float(max(dp[:, :, 0].max(), (dp[:, :, 1] / (1.0 + np.abs(part_gs[:, :, 1]))).max()))
+                print(f"[mx vs split] mode 2 M={M} N={N} K={K}: ln_part difference {part_d:.3e}")
                 assert part_d <= 2e-3 * max(1.0, a_amp), (M, N, K, part_d)              # the LayerNorm partials follow the rows
     finally:
         eng.close()
@@ -142,8 +200,8 @@ def test_fp8_range_guard_device_resident_forward_contract():
 
 def test_product_library_refuses_timing_only_stamped_and_deleted_kernels():
     """the product libgliclass_hip.so (plain `make`) contains no timing-only (wrong-result), stamped or rejected-experiment
-    kernel and no switch that reaches one: the attention microbenchmark refuses their variant bits and stamps, the MX GEMM check refuses the
-    modes of deleted kernels.  (A developer build — make DEV=1 — has the timing-only and stamped builds: skipped there.)"""
+    kernel and no switch that reaches one: the attention microbenchmark refuses their variant bits and stamps, the GEMM microbenchmark the
+    legs of deleted kernels.  (A developer build — make DEV=1 — has the timing-only and stamped builds: skipped there.)"""
     from gliclass.c_amd import _lib, synth
     from gliclass.c_amd.config import CONFIGS
     from gliclass.c_amd.engine import Engine
@@ -167,9 +225,7 @@ def test_product_library_refuses_timing_only_stamped_and_deleted_kernels():
             assert L.glc_debug_attn_bench(eng.h, 1, 128 | bits, 0, cs) < 0, bits
             assert b"no attention kernel takes these variant bits" in L.glc_last_error(), bits
         assert L.glc_debug_attn_bench(eng.h, 1, 128, 1, cs) < 0                      # stamps
-        out = (C.c_double * 8)()
-        for mode in (10, 20, 30):                                                    # (deleted) GY images, 16 x 16 shapes, 128 x 128 wave tile
-            assert L.glc_debug_gemm_mx_check(eng.h, 512, 768, 768, 1.0, 0.02, mode, out) != 0, mode
+        assert not hasattr(L, "glc_debug_gemm_mx_check")                             # the MX-vs-split check is a glc_debug_gemm_run test (above); its C entry is gone
         for which in (10, 11, 12, 13, 14, 1009):                                      # (deleted) stamped / GY / 16 x 16 / 128 x 128 MX GEMM legs, epilogue ablation
             assert L.glc_debug_gemm_bench(eng.h, 512, 768, 768, 0, 1, which) < 0, which
         assert not hasattr(L, "glc_debug_set_mx2")                                   # the bucket-space kernel's switch is gone with it
