@@ -52,9 +52,15 @@ class GLiClassConfig:
     local_window: int = 0
     global_every: int = 1
     rope_theta_local: float = 1.0e4
+    # decoder backbone: qk_norm = 1 is Qwen3's RMSNorm over head_dim on every query and key head before RoPE (gains q_norm / k_norm,
+    # epsilon ln_eps); attn_bias = 0 drops the q / k / v projection biases (Llama, Qwen3).  Qwen2 is (0, 1).
+    qk_norm: int = 0
+    attn_bias: int = 1
 
     def __post_init__(self):
-        assert self.hidden == self.heads * self.head_dim
+        # (a decoder checkpoint names its head_dim: Qwen3's is not hidden / heads)
+        assert self.backbone == BACKBONE_DECODER or self.hidden == self.heads * self.head_dim
+        assert self.qk_norm in (0, 1) and self.attn_bias in (0, 1) and (self.backbone == BACKBONE_DECODER or self.qk_norm == 0)
         if self.kv_heads <= 0:
             object.__setattr__(self, "kv_heads", self.heads)
         assert self.heads % self.kv_heads == 0
@@ -104,6 +110,17 @@ CONFIGS = {
                                ln_eps=1e-6, backbone=BACKBONE_DECODER, pooling=POOL_LAST),
     "qwen-1.5b": GLiClassConfig("qwen-1.5b", vocab=151648, hidden=1536, layers=28, heads=12, inter=8960, head_dim=128,
                                 kv_heads=2, ln_eps=1e-6, backbone=BACKBONE_DECODER, pooling=POOL_LAST),
+    # Qwen3 arithmetic (per-head QK RMSNorm, no projection biases): q3-tiny (head_dim 64, H % 256 != 0: the plain paths, nq d = H) and
+    # q3-mini (head_dim 128, nq d = 512 != H, group-split eligible) are the parity-fixture configs, qwen3-0.6b the published shape
+    # (vocab 151 936 + <<LABEL>>, <<SEP>>); ll-tiny is dec-tiny with Llama arithmetic (no biases, no QK norm)
+    "q3-tiny": GLiClassConfig("q3-tiny", vocab=515, hidden=128, layers=2, heads=2, inter=256, head_dim=64, kv_heads=1, ln_eps=1e-6,
+                              backbone=BACKBONE_DECODER, pooling=POOL_LAST, qk_norm=1, attn_bias=0),
+    "q3-mini": GLiClassConfig("q3-mini", vocab=1027, hidden=256, layers=3, heads=4, inter=768, head_dim=128, kv_heads=2, ln_eps=1e-6,
+                              backbone=BACKBONE_DECODER, pooling=POOL_LAST, qk_norm=1, attn_bias=0),
+    "ll-tiny": GLiClassConfig("ll-tiny", vocab=515, hidden=256, layers=2, heads=2, inter=512, head_dim=128, kv_heads=1, ln_eps=1e-6,
+                              backbone=BACKBONE_DECODER, pooling=POOL_LAST, qk_norm=0, attn_bias=0),
+    "qwen3-0.6b": GLiClassConfig("qwen3-0.6b", vocab=151938, hidden=1024, layers=28, heads=16, inter=3072, head_dim=128, kv_heads=8,
+                                 ln_eps=1e-6, backbone=BACKBONE_DECODER, pooling=POOL_LAST, qk_norm=1, attn_bias=0),
     # ModernBERT backbones: mb-tiny / mb-mini are the parity-fixture configs (mb-tiny: H % 256 != 0, the paths without group split;
     # mb-mini: group-split eligible), modernbert-base / -large the published shapes (vocab 50 368 + <<LABEL>>, <<SEP>>)
     "mb-tiny": GLiClassConfig("mb-tiny", vocab=515, hidden=128, layers=4, heads=2, inter=192, ln_eps=1e-5, backbone=BACKBONE_MODERNBERT,

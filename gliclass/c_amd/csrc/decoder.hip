@@ -5,6 +5,8 @@
 //   rmsnorm       Q2:247-252  w * x * rsqrt(mean(x^2) + eps), fp32 statistics, one wave per row
 //   rope_qk       Q2:86-100, 105-109, 133-134  rotate-half RoPE applied in place to the Q and K columns of the fused
 //                 QKV projection; the softmax scale log2(e)/sqrt(d) (Q2:186, :163) is folded into Q here
+//   qk norm       Qwen3 (models/qwen3/modeling_qwen3.py, Q3:237-238, 252-253): RMSNorm over head_dim on every Q and K head before
+//                 RoPE, inside the passes that read those elements anyway (rope_qk, qkv_layout; decoder_mx.hip qkv_layout_mx)
 //   swiglu        Q2:47       silu(gate) * up on the fused [gate | up] projection
 //   attn_gqa      Q2:160-170  grouped-query attention with causal and key-padding mask (create_causal_mask), exp2 softmax; with a
 //                 window W (ModernBERT's local layers, modeling_modernbert.py) keys with |q - k| > W are masked and never visited
@@ -120,9 +122,13 @@ __global__ __launch_bounds__(256) void swiglu_gs_kernel(const float* __restrict_
 }
 
 // In place on QKV [M, (nq + 2 nkv) d]: heads 0..nq-1 are Q (also scaled by qscale), nq..nq+nkv-1 are K.  cs = [Sp][d/2][2].
-template <typename T>
+// QKN (Qwen3, Q3:237-238): every Q / K head is RMS-normalised over its d elements before RoPE, y = g * (x * rsqrt(mean x^2 + eps)) with
+// g = qn for the Q heads and kn for the K heads, statistics in fp32.  d is 64 or 128 here, so the d/2 pairs of one head are the 32 or 64
+// lanes of ONE trip of the loop below (p = 64 k + lane: a head never straddles two trips, and at d = 64 the two heads of a trip sit in
+// the two 32-lane halves, each wholly inside or wholly outside npair): the sum of squares is finished by an xor-shuffle over those lanes.
+template <typename T, bool QKN = false>
 __global__ __launch_bounds__(256) void rope_qk_kernel(T* __restrict__ QKV, const float* __restrict__ cs, int M, int Sp, int nq, int nkv,
-                                                      int d, float qscale) {
+                                                      int d, float qscale, const float* __restrict__ qn, const float* __restrict__ kn, float eps) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
     const int s = row % Sp, hd2 = d >> 1, ld = (nq + 2 * nkv) * d;
@@ -132,7 +138,17 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(T* __restrict__ QKV, const
     for (int p = lane; p < npair; p += 64) {
         const int h = p / hd2, i = p - h * hd2;
         const float co = c[2 * i], sn = c[2 * i + 1];
-        const float x1 = (float)base[h * d + i], x2 = (float)base[h * d + i + hd2];
+        float x1 = (float)base[h * d + i], x2 = (float)base[h * d + i + hd2];
+        if constexpr (QKN) {
+            float ss = x1 * x1 + x2 * x2;
+#pragma unroll
+            for (int o = 1; o < 32; o <<= 1) ss += __shfl_xor(ss, o, 64);
+            if (hd2 == 64) ss += __shfl_xor(ss, 32, 64);                       // (wave-uniform)
+            const float rn = rsqrtf(ss / (float)d + eps);
+            const float* g = h < nq ? qn : kn;
+            x1 = g[i] * (x1 * rn);
+            x2 = g[i + hd2] * (x2 * rn);
+        }
         const float sc = h < nq ? qscale : 1.f;
         base[h * d + i] = (T)((x1 * co - x2 * sn) * sc);
         base[h * d + i + hd2] = (T)((x2 * co + x1 * sn) * sc);
@@ -282,9 +298,16 @@ template <bool GELU> static const char* launch_glu_gs(hipStream_t st, const floa
 const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<false>(st, GU, F, M, I); }
 const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<true>(st, GU, F, M, I); }
 
-const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale) {
+const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale,
+                               const float* qn, const float* kn, float eps) {
     if (M <= 0 || Sp <= 0 || !QKV || !cs || nq <= 0 || nkv <= 0 || d <= 0 || d % 2) return "rope: bad args";
-    DISPATCH_T(dtype, { hipLaunchKernelGGL(rope_qk_kernel<T>, dim3((M + 3) / 4), dim3(256), 0, st, (T*)QKV, cs, M, Sp, nq, nkv, d, qscale); });
+    if ((qn != nullptr) != (kn != nullptr)) return "rope: the QK norm takes both gains (q_norm and k_norm) or neither";
+    if (qn) {
+        if (d != 64 && d != 128) return "rope: the QK norm takes head_dim 64 or 128";
+        DISPATCH_T(dtype, { hipLaunchKernelGGL((rope_qk_kernel<T, true>), dim3((M + 3) / 4), dim3(256), 0, st, (T*)QKV, cs, M, Sp, nq, nkv, d, qscale, qn, kn, eps); });
+        return nullptr;
+    }
+    DISPATCH_T(dtype, { hipLaunchKernelGGL((rope_qk_kernel<T, false>), dim3((M + 3) / 4), dim3(256), 0, st, (T*)QKV, cs, M, Sp, nq, nkv, d, qscale, qn, kn, eps); });
     return nullptr;
 }
 
@@ -357,12 +380,17 @@ template <typename T, bool SPLIT> __device__ __forceinline__ void store_unit8(T*
     }
 }
 
-template <typename T, int D, bool SPLIT = false>
+// QKN (Qwen3, Q3:237-238): every Q / K head is RMS-normalised over its D elements before RoPE (gains qn / kn, fp32 statistics).  A thread
+// holds 16 of a head's elements; the head's D / 16 threads are consecutive lanes (idx = t, one trip of the loop: 32 (HD2 / 8) <= 256), the
+// group starts at a multiple of its size and 64 is a multiple of it, so it lies inside one wave and an xor-shuffle over it finishes the sum.
+template <typename T, int D, bool SPLIT = false, bool QKN = false>
 __global__ __launch_bounds__(256) void qkv_layout_kernel(const T* __restrict__ QKV, const float* __restrict__ cs, T* __restrict__ Qf,
-                                                         T* __restrict__ Kf, T* __restrict__ Vt, int Sp, int nq, int nkv, float qscale) {
+                                                         T* __restrict__ Kf, T* __restrict__ Vt, int Sp, int nq, int nkv, float qscale,
+                                                         const float* __restrict__ qn, const float* __restrict__ kn, float eps) {
     static_assert(!SPLIT || sizeof(T) == 4, "split units live in the fp32 layouts");
     typedef __attribute__((ext_vector_type(8))) T vec8;
     constexpr int HD2 = D / 2, NS = D / 16;
+    static_assert(32 * (HD2 / 8) <= 256 && 64 % (HD2 / 8) == 0, "QKN: a head's lanes share one wave and one trip of the RoPE loop");
     __shared__ T vs[32][D + 8];
     const int tile = blockIdx.x, head = blockIdx.y, t = threadIdx.x;           // tile over all B*Sp/32 row tiles
     const int ld = (nq + 2 * nkv) * D;
@@ -379,11 +407,27 @@ __global__ __launch_bounds__(256) void qkv_layout_kernel(const T* __restrict__ Q
             const float* c = cs + ((size_t)s * HD2 + c8 * 8) * 2;
             const float sc = isq ? qscale : 1.f;
             float o1[8], o2[8];
+            if constexpr (QKN) {
+                float xa[8], xb[8], ss = 0.f;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float co = c[2 * j], sn = c[2 * j + 1], x1 = (float)a[j], x2 = (float)bq[j];
-                o1[j] = (x1 * co - x2 * sn) * sc;
-                o2[j] = (x2 * co + x1 * sn) * sc;
+                for (int j = 0; j < 8; ++j) { xa[j] = (float)a[j]; xb[j] = (float)bq[j]; ss += xa[j] * xa[j] + xb[j] * xb[j]; }
+#pragma unroll
+                for (int o = 1; o < HD2 / 8; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                const float rn = rsqrtf(ss * (1.0f / (float)D) + eps);
+                const float* g = (isq ? qn : kn) + c8 * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float co = c[2 * j], sn = c[2 * j + 1], x1 = g[j] * (xa[j] * rn), x2 = g[HD2 + j] * (xb[j] * rn);
+                    o1[j] = (x1 * co - x2 * sn) * sc;
+                    o2[j] = (x2 * co + x1 * sn) * sc;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float co = c[2 * j], sn = c[2 * j + 1], x1 = (float)a[j], x2 = (float)bq[j];
+                    o1[j] = (x1 * co - x2 * sn) * sc;
+                    o2[j] = (x2 * co + x1 * sn) * sc;
+                }
             }
             const int lr = isq ? r : glc_pi32(r);                              // K rows sit at lane pi(r)
             T* dst = isq ? Qf + (((size_t)(b * nq + head) * nt + st) * NS) * 512 : Kf + (((size_t)(b * nkv + (head - nq)) * nt + st) * NS) * 512;
@@ -601,10 +645,13 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
 }
 
 template <typename T, bool SPLIT = false> const char* launch_layout_t(hipStream_t st, const void* QKV, const float* cs, void* Qf, void* Kf, void* Vt, int B, int Sp,
-                                                  int nq, int nkv, int d, float qscale) {
+                                                  int nq, int nkv, int d, float qscale, const float* qn, const float* kn, float eps) {
     const dim3 grid(B * Sp / 32, nq + 2 * nkv), block(256);
-    if (d == 128) hipLaunchKernelGGL((qkv_layout_kernel<T, 128, SPLIT>), grid, block, 0, st, (const T*)QKV, cs, (T*)Qf, (T*)Kf, (T*)Vt, Sp, nq, nkv, qscale);
-    else hipLaunchKernelGGL((qkv_layout_kernel<T, 64, SPLIT>), grid, block, 0, st, (const T*)QKV, cs, (T*)Qf, (T*)Kf, (T*)Vt, Sp, nq, nkv, qscale);
+#define GLC_LAYOUT(DD, QKN) hipLaunchKernelGGL((qkv_layout_kernel<T, DD, SPLIT, QKN>), grid, block, 0, st, (const T*)QKV, cs, (T*)Qf, (T*)Kf, (T*)Vt, Sp, nq, nkv, qscale, qn, kn, eps)
+    if (qn) { if (d == 128) GLC_LAYOUT(128, true); else GLC_LAYOUT(64, true); }
+    else if (d == 128) GLC_LAYOUT(128, false);
+    else GLC_LAYOUT(64, false);
+#undef GLC_LAYOUT
     return nullptr;
 }
 template <typename T, bool SPLIT = false> const char* launch_gqa_t(hipStream_t st, const void* Qf, const void* Kf, const void* Vt, const float* kbias, const int* klen,
@@ -624,12 +671,14 @@ template <typename T, bool SPLIT = false> const char* launch_gqa_t(hipStream_t s
 }  // namespace
 
 // RoPE + softmax scale + fragment-major layout of the fused projection (16-bit T).  Sp % 64 == 0, d in {64, 128}.
+// qn / kn: the per-head RMSNorm gains [d] of Qwen3's q_norm / k_norm (eps its epsilon), applied before RoPE; both null = no norm.
 const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, const float* cs, void* Qf, void* Kf, void* Vt, int B, int Sp,
-                                  int nq, int nkv, int d, float qscale) {
+                                  int nq, int nkv, int d, float qscale, const float* qn, const float* kn, float eps) {
     if (!QKV || !cs || !Qf || !Kf || !Vt || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || (d != 64 && d != 128)) return "qkv_layout: bad args";
-    if (dtype == GLC_DT_BF16) return launch_layout_t<bf16_t>(st, QKV, cs, Qf, Kf, Vt, B, Sp, nq, nkv, d, qscale);
-    if (dtype == GLC_DT_F16) return launch_layout_t<f16_t>(st, QKV, cs, Qf, Kf, Vt, B, Sp, nq, nkv, d, qscale);
-    if (dtype == GLC_DT_F32) return launch_layout_t<float, true>(st, QKV, cs, Qf, Kf, Vt, B, Sp, nq, nkv, d, qscale);    // fp32 data -> split-f16 units
+    if ((qn != nullptr) != (kn != nullptr)) return "qkv_layout: the QK norm takes both gains (q_norm and k_norm) or neither";
+    if (dtype == GLC_DT_BF16) return launch_layout_t<bf16_t>(st, QKV, cs, Qf, Kf, Vt, B, Sp, nq, nkv, d, qscale, qn, kn, eps);
+    if (dtype == GLC_DT_F16) return launch_layout_t<f16_t>(st, QKV, cs, Qf, Kf, Vt, B, Sp, nq, nkv, d, qscale, qn, kn, eps);
+    if (dtype == GLC_DT_F32) return launch_layout_t<float, true>(st, QKV, cs, Qf, Kf, Vt, B, Sp, nq, nkv, d, qscale, qn, kn, eps);    // fp32 data -> split-f16 units
     return "qkv_layout: bad dtype";
 }
 

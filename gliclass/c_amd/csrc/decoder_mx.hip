@@ -27,11 +27,15 @@ __device__ __forceinline__ i32x8 cat8(const i32x4& a, const i32x4& b) {
     return r;
 }
 
-template <int D>
+// QKN (Qwen3's q_norm / k_norm, as decoder.hip qkv_layout_kernel): RMSNorm over the head's D elements before RoPE; the head's D / 16 threads
+// are consecutive lanes of one wave in the one trip of the loop, an xor-shuffle over them finishes the sum of squares.  The MX-tile writer
+// (and with it the fp8 range counter) sees the normalised, rotated values.
+template <int D, bool QKN = false>
 __global__ __launch_bounds__(256) void qkv_layout_mx_kernel(const float* __restrict__ QKV, const float* __restrict__ cs, unsigned char* __restrict__ Qm,
                                                             unsigned char* __restrict__ Km, unsigned char* __restrict__ Vm, int Sp, int nq, int nkv, float qscale,
-                                                            unsigned* sat) {
+                                                            unsigned* sat, const float* __restrict__ qn, const float* __restrict__ kn, float eps) {
     constexpr int HD2 = D / 2, NS = D / 16, TILE = 32 * D * 4;
+    static_assert(32 * (HD2 / 8) <= 256 && 64 % (HD2 / 8) == 0, "QKN: a head's lanes share one wave and one trip of the RoPE loop");
     __shared__ float vs[32][D + 4];
     const int tile = blockIdx.x, head = blockIdx.y, t = threadIdx.x;           // tile over all B*Sp/32 row tiles
     const int ld = (nq + 2 * nkv) * D;
@@ -45,7 +49,18 @@ __global__ __launch_bounds__(256) void qkv_layout_mx_kernel(const float* __restr
             const float* src = QKV + (size_t)(m0 + r) * ld + (size_t)head * D + c8 * 8;
             const f32x4 a0 = *reinterpret_cast<const f32x4*>(src), a1 = *reinterpret_cast<const f32x4*>(src + 4);
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(src + HD2), b1 = *reinterpret_cast<const f32x4*>(src + HD2 + 4);
-            const float x1[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]}, x2[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+            float x1[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]}, x2[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+            if constexpr (QKN) {
+                float ss = 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss += x1[j] * x1[j] + x2[j] * x2[j];
+#pragma unroll
+                for (int o = 1; o < HD2 / 8; o <<= 1) ss += __shfl_xor(ss, o, 64);
+                const float rn = rsqrtf(ss * (1.0f / (float)D) + eps);
+                const float* g = (isq ? qn : kn) + c8 * 8;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { x1[j] = g[j] * (x1[j] * rn); x2[j] = g[HD2 + j] * (x2[j] * rn); }
+            }
             const float* c = cs + ((size_t)s * HD2 + c8 * 8) * 2;
             const float sc = isq ? qscale : 1.f;
             float o1[8], o2[8];
@@ -481,12 +496,18 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_ring_kernel(const unsigned
 }  // namespace
 
 // RoPE + softmax scale + MX tiles of the fused fp32 projection.  Sp % 64 == 0, d in {64, 128}; Qm / Km / Vm: 4 bytes per element.
-const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const float* cs, void* Qm, void* Km, void* Vm, int B, int Sp, int nq, int nkv, int d, float qscale) {
+// qn / kn: the gains [d] of Qwen3's q_norm / k_norm (eps its epsilon), applied per head before RoPE; both null = no norm.
+const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const float* cs, void* Qm, void* Km, void* Vm, int B, int Sp, int nq, int nkv, int d, float qscale,
+                                     const float* qn, const float* kn, float eps) {
     if (!QKV || !cs || !Qm || !Km || !Vm || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || (d != 64 && d != 128)) return "qkv_layout_mx: bad args";
+    if ((qn != nullptr) != (kn != nullptr)) return "qkv_layout_mx: the QK norm takes both gains (q_norm and k_norm) or neither";
     const dim3 grid(B * Sp / 32, nq + 2 * nkv), block(256);
     unsigned* sat = glc_gx_sat_ptr();
-    if (d == 128) hipLaunchKernelGGL(qkv_layout_mx_kernel<128>, grid, block, 0, st, (const float*)QKV, cs, (unsigned char*)Qm, (unsigned char*)Km, (unsigned char*)Vm, Sp, nq, nkv, qscale, sat);
-    else hipLaunchKernelGGL(qkv_layout_mx_kernel<64>, grid, block, 0, st, (const float*)QKV, cs, (unsigned char*)Qm, (unsigned char*)Km, (unsigned char*)Vm, Sp, nq, nkv, qscale, sat);
+#define GLC_LAYOUT_MX(DD, QKN) hipLaunchKernelGGL((qkv_layout_mx_kernel<DD, QKN>), grid, block, 0, st, (const float*)QKV, cs, (unsigned char*)Qm, (unsigned char*)Km, (unsigned char*)Vm, Sp, nq, nkv, qscale, sat, qn, kn, eps)
+    if (qn) { if (d == 128) GLC_LAYOUT_MX(128, true); else GLC_LAYOUT_MX(64, true); }
+    else if (d == 128) GLC_LAYOUT_MX(128, false);
+    else GLC_LAYOUT_MX(64, false);
+#undef GLC_LAYOUT_MX
     return nullptr;
 }
 

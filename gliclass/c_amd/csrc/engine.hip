@@ -321,16 +321,20 @@ static bool build_mx_weights_impl(glc_engine* e, std::vector<void**>& made) {
             if (!copy(w.Wqkvf, NQKV * H, w.Wqkvf_x, w.ws_qkvf) || !copy(w.Wo, H * NQ, w.Wo_x, w.ws_o) ||
                 !copy(w.Wguf, 2 * I * H, w.Wguf_x, w.ws_guf) || !copy(w.Wd, H * I, w.Wd_x, w.ws_d)) return false;
             if (!rope_epi) continue;
-            w.bqkv_p = (float*)dmalloc(e, NQKV * sizeof(float), false);
-            if (!w.bqkv_p) return false;
-            made.push_back(reinterpret_cast<void**>(&w.bqkv_p));
-            HIPCHK(hipMemcpyAsync(w.bqkv_p, w.bqkv, NQKV * sizeof(float), hipMemcpyDeviceToDevice, e->stream), false);
+            if (w.bqkv) {                                     // (no biases — Llama, Qwen3 — no permuted copy: the permuted weight alone says so)
+                w.bqkv_p = (float*)dmalloc(e, NQKV * sizeof(float), false);
+                if (!w.bqkv_p) return false;
+                made.push_back(reinterpret_cast<void**>(&w.bqkv_p));
+                HIPCHK(hipMemcpyAsync(w.bqkv_p, w.bqkv, NQKV * sizeof(float), hipMemcpyDeviceToDevice, e->stream), false);
+            }
+            w.qkv_perm = true;
             for (int hd = 0; hd < c.heads + c.kv_heads; ++hd) {
                 char* r1 = (char*)w.Wqkvf_x + ((size_t)hd * 128 + 32) * H * sizeof(float);
                 char* r2 = r1 + blk;
                 HIPCHK(hipMemcpyAsync(tmp, r1, blk, hipMemcpyDeviceToDevice, e->stream), false);
                 HIPCHK(hipMemcpyAsync(r1, r2, blk, hipMemcpyDeviceToDevice, e->stream), false);
                 HIPCHK(hipMemcpyAsync(r2, tmp, blk, hipMemcpyDeviceToDevice, e->stream), false);
+                if (!w.bqkv_p) continue;
                 HIPCHK(hipMemcpyAsync(w.bqkv_p + hd * 128 + 32, w.bqkv + hd * 128 + 64, 32 * sizeof(float), hipMemcpyDeviceToDevice, e->stream), false);
                 HIPCHK(hipMemcpyAsync(w.bqkv_p + hd * 128 + 64, w.bqkv + hd * 128 + 32, 32 * sizeof(float), hipMemcpyDeviceToDevice, e->stream), false);
             }
@@ -358,6 +362,7 @@ bool build_mx_weights(glc_engine* e) {
     (void)hipStreamSynchronize(e->stream);
     (void)hipGetLastError();
     for (void** slot : made) { dfree(e, *slot); *slot = nullptr; }
+    for (auto& w : e->dlayers) w.qkv_perm = false;
     e->mx_bytes = 0;
     e->mx_built = false;
     e->mx = false;
@@ -542,6 +547,7 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
     e->last_mx = mx;
     const bool mxa = mx && mfma && e->mx_attn;      // round 4: the attention of the MX pipeline on MX tiles too (decoder_mx.hip)
     e->last_mx_attn = mxa;
+    e->last_rope_epi = false;
     const GemmGs gemm_gs{st, mx, M};
     if (rnf) {      // the embedding rows enter the pipeline: plain fp32 (X2) -> raw group-split rows (X) + statistics
         HIPCHK(hipMemcpyAsync(e->X2, e->X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
@@ -555,17 +561,23 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
         g.A = e->H1; g.W = w.Wqkv; g.bias = w.bqkv; g.C = e->QKV; g.Mpad = Mpad; g.N = NQKV; g.K = H; g.gs_c_plain = 1;
         if (rnf) { g.A = X; g.W = w.Wqkvf; g.a_stats = sX; }
         if (mx) { g.W = w.Wqkvf_x; g.mx_ws = w.ws_qkvf; }
-        const bool perm = mx && w.bqkv_p;            // Wqkvf_x rows in the RoPE-epilogue order
+        const bool perm = mx && w.qkv_perm;          // Wqkvf_x rows in the RoPE-epilogue order (bqkv_p with them, null for a bias-free model)
         if (perm) { g.bias = w.bqkv_p; g.perm_cols = (nq + nkv) * d; }
-        const bool rope_epi = perm && mxa;           // Q2:206-211 in one launch: projection, RoPE, scale, MX tiles (gemm256x.hip EPI_QKVR)
+        // Q2:206-211 in one launch: projection, RoPE, scale, MX tiles (gemm256x.hip EPI_QKVR).  Not with qk_norm (Qwen3, Q3:237-238): the norm
+        // needs a head's 128 columns together and the epilogue holds them in more than one wave's sub-tile, so the plain projection (its
+        // epilogue puts the permuted columns back) and the layout pass below, which carries the norm, run instead: one more pass over
+        // the QKV rows per layer on the MX pipeline, for Qwen3 only (not measured).
+        const bool rope_epi = perm && mxa && !c.qk_norm;
+        if (l == 0) e->last_rope_epi = rope_epi;
         if (rope_epi) { g.rope_cs = e->ropes[{Sp, c.rope_theta}]; g.qscale = qscale; g.nq = nq; g.nkv = nkv; g.Sp = Sp; g.Mvalid = M; g.Qh = e->Qh; g.Kh = e->Kh; g.Vt = e->Vt; }
         { Prof p(e, PC_QKV);
           if (rope_epi) KCHK(gemm_gs(EPI_QKVR, g), false);
           else {
           KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);        // Q2:206-208
-          if (mxa) KCHK(glc_launch_qkv_layout_mx(st, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale), false);     // Q2:211 RoPE, MX tiles (decoder_mx.hip)
-          else if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale), false);   // Q2:211 RoPE
-          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], M, Sp, nq, nkv, d, qscale), false); } }
+          // (w.qn / w.kn: Qwen3's per-head RMSNorm, Q3:237-238, inside whichever of the three passes runs; null otherwise)
+          if (mxa) KCHK(glc_launch_qkv_layout_mx(st, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale, w.qn, w.kn, c.ln_eps), false);     // Q2:211 RoPE, MX tiles (decoder_mx.hip)
+          else if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale, w.qn, w.kn, c.ln_eps), false);   // Q2:211 RoPE
+          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], M, Sp, nq, nkv, d, qscale, w.qn, w.kn, c.ln_eps), false); } }
         { Prof p(e, PC_ATTN);
           if (mxa) KCHK(glc_launch_attention_gqa_mx(st, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal), false);
           else if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal, mx ? 2 : (gs ? 1 : 0)), false);
@@ -908,8 +920,19 @@ bool create_decoder(glc_engine* e, const float* const* tensors, float* staging) 
     const size_t NQ = (size_t)c.heads * d, NKV = (size_t)c.kv_heads * d, NQKV = NQ + 2 * NKV, IH = (size_t)I * H;
     e->dlayers.resize(L);
     std::vector<float> bqkv(NQKV), gu_host, fold_host;
+    const int per = glc_dec_tensors_per_layer(&c);
     for (int l = 0; l < L; ++l) {
-        const float* const* t = tensors + 1 + GLC_DEC_TENSORS_PER_LAYER * l;    // ln1 qw qb kw kb vw vb ow ln2 gw uw dw
+        // the layer's tensors in the Qwen2 numbering whatever the model carries (include/gliclass_hip.h): ln1 qw qb kw kb vw vb ow ln2 gw uw dw,
+        // then q_norm, k_norm; absent ones (the biases without attn_bias, the gains without qk_norm) stay null
+        const float* t[14] = {nullptr};
+        {
+            const float* const* src = tensors + 1 + per * l;
+            int j = 0;
+            t[0] = src[j++];
+            for (int k = 1; k <= 5; k += 2) { t[k] = src[j++]; if (c.attn_bias) t[k + 1] = src[j++]; }
+            if (c.qk_norm) { t[12] = src[j++]; t[13] = src[j++]; }
+            for (int k = 7; k <= 11; ++k) t[k] = src[j++];
+        }
         DecLayerW& w = e->dlayers[l];
         if (e->fused_swiglu) interleave_glu_rows(t[9], t[10], I, H, gu_host);
         const Proj gu = e->fused_swiglu ? Proj{&w.Wgu, {{gu_host.data(), 2 * IH}}} : Proj{&w.Wgu, {{t[9], IH}, {t[10], IH}}};
@@ -927,14 +950,21 @@ bool create_decoder(glc_engine* e, const float* const* tensors, float* staging) 
             fold_rows(gu_host.data(), 2 * (size_t)I, t[8], wf.data());           // the interleaved [16 gate | 16 up] row order is kept
             if (!upload_projections(e, staging, {{&w.Wguf, {{wf.data(), 2 * IH}}}})) return false;
         }
-        for (size_t i = 0; i < NQ; ++i) bqkv[i] = t[2][i];
-        for (size_t i = 0; i < NKV; ++i) { bqkv[NQ + i] = t[4][i]; bqkv[NQ + NKV + i] = t[6][i]; }
-        w.bqkv = upload_f32(e, bqkv.data(), NQKV);
+        if (c.attn_bias) {
+            for (size_t i = 0; i < NQ; ++i) bqkv[i] = t[2][i];
+            for (size_t i = 0; i < NKV; ++i) { bqkv[NQ + i] = t[4][i]; bqkv[NQ + NKV + i] = t[6][i]; }
+            w.bqkv = upload_f32(e, bqkv.data(), NQKV);
+            if (!w.bqkv) return false;
+        }
+        if (c.qk_norm) {
+            w.qn = upload_f32(e, t[12], d); w.kn = upload_f32(e, t[13], d);
+            if (!w.qn || !w.kn) return false;
+        }
         w.ln1 = upload_f32(e, t[0], H); w.ln2 = upload_f32(e, t[8], H);
-        if (!w.bqkv || !w.ln1 || !w.ln2) return false;
+        if (!w.ln1 || !w.ln2) return false;
         if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err("sync failed"); return false; }   // bqkv host buffer is reused
     }
-    e->final_norm = upload_f32(e, tensors[1 + GLC_DEC_TENSORS_PER_LAYER * L], H);
+    e->final_norm = upload_f32(e, tensors[1 + per * L], H);
     return e->final_norm != nullptr;
 }
 
@@ -1139,6 +1169,8 @@ void glc_delta_table(int S, int bucket_size, int max_position, int32_t* out) {
 glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* tensors, int n_tensors, int device, int dtype) {
     if (!cfg || !tensors) { glc_set_err("engine_create: null argument"); return nullptr; }
     if (dtype != GLC_F32 && dtype != GLC_BF16 && dtype != GLC_F16) { glc_set_err("engine_create: bad dtype"); return nullptr; }
+    if ((cfg->qk_norm & ~1) || (cfg->attn_bias & ~1)) { glc_set_err("engine_create: qk_norm and attn_bias must be 0 or 1"); return nullptr; }
+    if (cfg->qk_norm && cfg->backbone != GLC_BACKBONE_DECODER) { glc_set_err("engine_create: qk_norm = 1 (per-head RMSNorm on Q and K) exists on the decoder backbone only"); return nullptr; }
     if (n_tensors != glc_num_tensors_cfg(cfg)) { glc_set_err("engine_create: wrong tensor count"); return nullptr; }
     for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { glc_set_err("engine_create: null tensor"); return nullptr; }
     const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT;
@@ -1571,6 +1603,7 @@ int glc_debug_set_mx(glc_engine* e, int on) {
 }
 int glc_debug_last_forward_mx(const glc_engine* e) { return e ? (e->last_mx ? 1 : 0) : -1; }
 int glc_debug_last_forward_mx_attention(const glc_engine* e) { return e ? (e->last_mx && e->last_mx_attn ? 1 : 0) : -1; }
+int glc_debug_last_forward_rope_epilogue(const glc_engine* e) { return e ? (e->last_mx && e->last_mx_attn && e->last_rope_epi ? 1 : 0) : -1; }
 /* MX pipeline: attention on MX tiles (1, default) or on split-f16 units (0). */
 int glc_debug_set_mx_attention(glc_engine* e, int on) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); e->mx_attn = on != 0; return 0; }
 /* Developer: stop the next forwards after stage 10 * layer + k (k = 0 QKV, 1 attention, 2 attention-output, 3 FFN1, 4 FFN2 + LayerNorm;

@@ -37,11 +37,13 @@ const char* const kProfNames[PC_N] = {"scan_rows", "embed_ln", "gemm_qkv", "atte
 
 struct DecLayerW {                     // decoder-style backbone (decoder.hip)
     void *Wqkv = nullptr, *Wo = nullptr, *Wgu = nullptr, *Wd = nullptr;       // T: [(nq+2nkv)d, H], [H, nq d], [2I, H] (gate rows | up rows), [H, I]
-    float *bqkv = nullptr, *ln1 = nullptr, *ln2 = nullptr;                    // f32
+    float *bqkv = nullptr, *ln1 = nullptr, *ln2 = nullptr;                    // f32 (bqkv: null without attn_bias — Llama, Qwen3)
     void *Wqkvf = nullptr, *Wguf = nullptr;                                   // fp32 mode, RMSNorm folded into the GEMMs: Wqkv diag(ln1), Wgu diag(ln2), group-split
     void *Wqkvf_x = nullptr, *Wo_x = nullptr, *Wguf_x = nullptr, *Wd_x = nullptr;   // MX pipeline: the same four as GX rows + their fp8 exponents
     int ws_qkvf = 0, ws_o = 0, ws_guf = 0, ws_d = 0;
     float* bqkv_p = nullptr;            // bqkv in the row order of a Wqkvf_x built for the RoPE epilogue (glc_rope_perm128), else null
+    bool qkv_perm = false;              // Wqkvf_x's rows are in that order (with or without a bias to go with them)
+    float *qn = nullptr, *kn = nullptr; // qk_norm (Qwen3): the gains [head_dim] of self_attn.q_norm / k_norm, f32; else null
 };
 
 struct LayerW {
@@ -72,6 +74,7 @@ struct glc_engine {
     size_t mx_bytes = 0;                 // their size (glc_debug_mx_weight_bytes)
     bool last_mx = false;                // the last forward ran the MX pipeline
     bool last_mx_attn = false;           // ... and its attention ran on MX tiles (attention_mx.hip)
+    bool last_rope_epi = false;          // ... and (decoder) its QKV projections ran RoPE + MX tiles as their epilogue (gemm256x EPI_QKVR)
     bool dec_rope_epi = true;            // decoder MX pipeline: RoPE + MX tiles as the QKV projection's epilogue (gemm256x EPI_QKVR); GLC_DEC_ROPE_EPI=0: the separate pass
     bool mx_attn = true;                 // MX pipeline: attention on MX tiles (attention_mx.hip); false: split-f16 units (GLC_MX_ATTN=0, glc_debug_set_mx_attention)
     int debug_stop = -1;                 // developer: leave run_forward after stage (10 * layer + k), k = 0 QKV, 1 attention, 2 attn-out, 3 FFN1, 4 FFN2 (+ LayerNorm): workspace inspection

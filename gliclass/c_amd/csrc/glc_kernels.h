@@ -258,7 +258,10 @@ const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_
 const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I);       // gelu(GU[m, i]) * GU[m, I + i] (ModernBERT)
 const char* glc_launch_rmsnorm(hipStream_t st, int dtype, const void* X, void* Y, const float* w, float eps, int M, int H);
 // in-place rotate-half RoPE on the Q and K heads of QKV [M, (nq+2nkv) d]; cs = [Sp][d/2][cos,sin]; Q additionally * qscale
-const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale);
+// qn / kn (here and in the two layout passes below): gains [d] of Qwen3's per-head RMSNorm on the Q / K heads (eps its epsilon), applied before
+// RoPE and the scale; both null = no norm, exactly one = an error string
+const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale,
+                               const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
 // F[m,i] = silu(GU[m,i]) * GU[m,I+i]
 const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter = 0);   // inter: 16 gate / 16 up interleaved columns
 // F[m,i] = gelu(GU[m,i]) * GU[m,I+i] (ModernBERT's GeGLU on [input | gate]; erf GELU); inter as above
@@ -268,7 +271,7 @@ const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const 
                                      int B, int Sp, int nq, int nkv, int d, int causal, int window = 0);   // window > 0: keys |q - k| <= window only
 // 16-bit MFMA path: RoPE + scale + fragment-major Q / K / V^T (layouts in decoder.hip), then the flash-style kernel
 const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, const float* cs, void* Qf, void* Kf, void* Vt, int B, int Sp,
-                                  int nq, int nkv, int d, float qscale);
+                                  int nq, int nkv, int d, float qscale, const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
 // ctx_gs (fp32 mode only): write the context rows in the group-split format
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0,
@@ -276,7 +279,8 @@ const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void*
 
 // MX pipeline (decoder_mx.hip, round 4): the fused fp32 projection -> RoPE + scale + MX tiles (f16 hi units + fp8 steps, 4 bytes per element),
 // and the grouped-query attention on them (a_hi*b_hi in f16 MFMAs + both cross terms in one block-scaled fp8 MFMA); CTX as GX rows
-const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const float* cs, void* Qm, void* Km, void* Vm, int B, int Sp, int nq, int nkv, int d, float qscale);
+const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const float* cs, void* Qm, void* Km, void* Vm, int B, int Sp, int nq, int nkv, int d, float qscale,
+                                     const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
 const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const void* Km, const void* Vm, const float* kbias, const int* klen, const int* kfirst, void* CTX,
                                         int B, int Sp, int nq, int nkv, int d, int causal);
 

@@ -17,7 +17,7 @@ def to_c_config(cfg: GLiClassConfig) -> _lib.ModelConfig:
                             cfg.max_rel_pos, cfg.pad_id, cfg.cls_id, cfg.sep_id, cfg.class_token_index, cfg.text_token_index,
                             cfg.pooling, cfg.scorer, cfg.embed_class_token, cfg.normalize_features, cfg.backbone, cfg.kv_heads,
                             cfg.causal, cfg.ln_eps, cfg.logit_scale, cfg.rope_theta, cfg.local_window, cfg.global_every,
-                            cfg.rope_theta_local)
+                            cfg.rope_theta_local, cfg.qk_norm, cfg.attn_bias)
 
 
 def delta_table(S, bucket_size=256, max_position=512):
@@ -132,6 +132,10 @@ class Engine:
     def last_mx_attention(self):
         """the last forward's attention ran on MX tiles (attention_mx.hip)"""
         return bool(self.L.glc_debug_last_forward_mx_attention(self.h))
+
+    def last_rope_epilogue(self):
+        """decoder, MX pipeline: the last forward's QKV projections ran RoPE + MX tiles as their epilogue (never with qk_norm)"""
+        return bool(self.L.glc_debug_last_forward_rope_epilogue(self.h))
 
     def fp8_range_retries(self):
         """host-buffer forwards repeated on the split-f16 kernels because an activation left the fp8 range of the MX operand images"""

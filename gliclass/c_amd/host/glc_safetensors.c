@@ -6,7 +6,7 @@
  * config.json and the safetensors header (8-byte little-endian length, JSON {"name": {"dtype","shape","data_offsets"}},
  * raw little-endian tensor data); F32 / F16 / BF16 tensors are widened to fp32.
  *
- * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `ModernBertModel` state_dict) under any of the prefixes GLiClass checkpoints use;
+ * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `Qwen3Model` / `LlamaModel` / `ModernBertModel` state_dict) under any of the prefixes GLiClass checkpoints use;
  * configuration fields follow transformers' DebertaV2Config / Qwen2Config inside `encoder_config`, and the GLiClass
  * fields as restated in SURVEY.md §8a row a12 (class_token_index, text_token_index, pooling_strategy, scorer_type,
  * embed_class_token, normalize_features ...).  The GLiClass field names come from the upstream python package, which
@@ -107,6 +107,7 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
     c->vocab = (int32_t)jnum(root, "vocab_size", jnum(enc, "vocab_size", 0));
     if (c->hidden <= 0 || c->layers <= 0 || c->heads <= 0 || c->inter <= 0 || c->hidden % c->heads) REJECT("missing or inconsistent backbone dimensions");
     c->head_dim = c->hidden / c->heads;
+    c->qk_norm = 0; c->attn_bias = 1;
     if (!strcmp(mt, "deberta-v2")) {
         c->backbone = GLC_BACKBONE_DEBERTA;
         c->kv_heads = c->heads; c->causal = 1; c->rope_theta = 1.0e6f;   /* unused by this backbone; the blob header's defaults */
@@ -134,6 +135,38 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
         c->pos_buckets = 0; c->max_rel_pos = 0;
         if (!pool) c->pooling = GLC_POOL_LAST;
         if (c->kv_heads <= 0 || c->heads % c->kv_heads) REJECT("num_key_value_heads does not divide num_attention_heads");
+    } else if (!strcmp(mt, "qwen3") || !strcmp(mt, "llama")) {
+        /* transformers models/qwen3 (per-head RMSNorm on Q and K before RoPE, its own head_dim) and models/llama: the Qwen2 stack without
+         * (or, attention_bias: true, with) the q / k / v biases.  Anything that changes the arithmetic beyond that is refused by name. */
+        c->backbone = GLC_BACKBONE_DECODER;
+        c->qk_norm = !strcmp(mt, "qwen3");
+        c->attn_bias = jflag(enc, "attention_bias", 0);
+        c->head_dim = (int32_t)jnum(enc, "head_dim", (double)(c->hidden / c->heads));
+        c->kv_heads = (int32_t)jnum(enc, "num_key_value_heads", c->heads);
+        c->causal = jflag(root, "causal", 1);
+        c->ln_eps = (float)jnum(enc, "rms_norm_eps", 1e-6);
+        c->rope_theta = (float)jnum(enc, "rope_theta", c->qk_norm ? 1.0e6 : 1.0e4);
+        c->pos_buckets = 0; c->max_rel_pos = 0;
+        if (!pool) c->pooling = GLC_POOL_LAST;
+        if (c->kv_heads <= 0 || c->heads % c->kv_heads) REJECT("num_key_value_heads does not divide num_attention_heads");
+        if (c->head_dim != 64 && c->head_dim != 128) REJECT("head_dim %d is not implemented (64, 128)", c->head_dim);
+        if (jflag(enc, "mlp_bias", 0)) REJECT("mlp_bias=true is not implemented");
+        if (jflag(enc, "use_sliding_window", 0)) REJECT("use_sliding_window=true is not implemented");
+        const gj_value* lt = gj_get(enc, "layer_types");
+        if (gj_is(lt, GJ_ARR) && list_has(lt, "sliding_attention")) REJECT("layer_types with a 'sliding_attention' entry is not implemented");
+        const char* act = jtext(enc, "hidden_act");
+        if (act && strcmp(act, "silu")) REJECT("hidden_act '%s' is not implemented (silu)", act);
+        /* RoPE: the default rotation only (Llama-3.x frequency scaling, linear / dynamic / yarn are out of scope).  transformers 4 writes
+         * rope_scaling {rope_type | type}, transformers 5 rope_parameters {rope_type, rope_theta}. */
+        static const char* const rk[2] = {"rope_scaling", "rope_parameters"};
+        for (int q = 0; q < 2; ++q) {
+            const gj_value* rs = gj_get(enc, rk[q]);
+            if (!gj_is(rs, GJ_OBJ)) continue;
+            const char* rt = jtext(rs, "rope_type");
+            if (!rt) rt = jtext(rs, "type");
+            if (rt && strcmp(rt, "default")) REJECT("%s type '%s' is not implemented (default)", rk[q], rt);
+            c->rope_theta = (float)jnum(rs, "rope_theta", c->rope_theta);
+        }
     } else if (!strcmp(mt, "modernbert")) {
         /* transformers models/modernbert: configuration_modernbert.py (both the transformers-5 form with layer_types / rope_parameters
          * and the older one with global_attn_every_n_layers / global_rope_theta / local_rope_theta) */
@@ -181,7 +214,7 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
             const char* rs = gj_is(sa, GJ_OBJ) ? jtext(sa, "rope_type") : NULL;
             if ((rt && strcmp(rt, "default")) || (rs && strcmp(rs, "default"))) REJECT("rope_type other than 'default' is not implemented");
         }
-    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, modernbert)", mt);
+    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, qwen3, llama, modernbert)", mt);
     return 0;
 }
 
@@ -261,6 +294,18 @@ int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
     if (c->class_token_index < 0) c->class_token_index = c->vocab - 2;
     if (c->text_token_index < 0) c->text_token_index = c->vocab - 1;
 
+    if (c->backbone == GLC_BACKBONE_DECODER) {
+        /* q_norm / k_norm exactly when the configuration says so: a checkpoint that carries gains the forward would not apply (or lacks
+         * the ones it would) is another model than its config.json names */
+        static const char* const qk[2] = {"layers.0.self_attn.q_norm.weight", "layers.0.self_attn.k_norm.weight"};
+        for (int q = 0; q < 2; ++q) {
+            const int have = st_find(&st, qk[q], found, sizeof found) != NULL;
+            if (have && !c->qk_norm) { fprintf(stderr, "Error: '%s': tensor '%s' is present, but this model_type has no q_norm / k_norm\n", stp, found); goto done; }
+            if (!have && c->qk_norm) { fprintf(stderr, "Error: '%s': tensor '%s' is missing (model_type qwen3 needs q_norm and k_norm)\n", stp, qk[q]); goto done; }
+        }
+        /* (Llama / Qwen3 with attention_bias: true give o_proj a bias as well; the tensor order has no slot for it) */
+        if (st_find(&st, "layers.0.self_attn.o_proj.bias", found, sizeof found)) { fprintf(stderr, "Error: '%s': tensor '%s' (an output-projection bias) is not implemented\n", stp, found); goto done; }
+    }
     w->n_tensors = glc_num_tensors_cfg(c);
     w->tensors = (const float**)calloc((size_t)w->n_tensors, sizeof(float*));
     if (!w->tensors) goto done;

@@ -54,23 +54,28 @@ int glc_named_config(const char* name, glc_model_config* c) {
             c->class_token_index = c->vocab - 2; c->text_token_index = c->vocab - 1;
             c->pooling = GLC_POOL_FIRST; c->scorer = GLC_SCORER_DOT; c->embed_class_token = 1; c->normalize_features = 0;
             c->backbone = GLC_BACKBONE_DEBERTA; c->kv_heads = c->heads; c->causal = 1; c->rope_theta = 1.0e6f;
-            c->ln_eps = 1e-7f; c->logit_scale = 1.0f;
+            c->ln_eps = 1e-7f; c->logit_scale = 1.0f; c->attn_bias = 1;
             return 0;
         }
-    /* decoder-style backbones (config.py CONFIGS "dec-tiny", "dec-mini", "qwen-1.5b") */
-    static const struct { const char* n; int vocab, hidden, layers, heads, kv, inter; } D[] = {
-        {"dec-tiny", 515, 256, 2, 2, 1, 512}, {"dec-mini", 1027, 512, 3, 4, 2, 768}, {"qwen-1.5b", 151648, 1536, 28, 12, 2, 8960},
+    /* decoder-style backbones (config.py CONFIGS "dec-tiny", "dec-mini", "qwen-1.5b": Qwen2 arithmetic; "q3-tiny", "q3-mini", "qwen3-0.6b": Qwen3,
+     * per-head QK RMSNorm and no projection biases; "ll-tiny": Llama, neither) */
+    static const struct { const char* n; int vocab, hidden, layers, heads, kv, hd, inter, qkn, ab; } D[] = {
+        {"dec-tiny", 515, 256, 2, 2, 1, 128, 512, 0, 1},  {"dec-mini", 1027, 512, 3, 4, 2, 128, 768, 0, 1},
+        {"qwen-1.5b", 151648, 1536, 28, 12, 2, 128, 8960, 0, 1},
+        {"q3-tiny", 515, 128, 2, 2, 1, 64, 256, 1, 0},    {"q3-mini", 1027, 256, 3, 4, 2, 128, 768, 1, 0},
+        {"ll-tiny", 515, 256, 2, 2, 1, 128, 512, 0, 0},   {"qwen3-0.6b", 151938, 1024, 28, 16, 8, 128, 3072, 1, 0},
     };
     for (size_t i = 0; i < sizeof(D) / sizeof(D[0]); ++i)
         if (strcmp(name, D[i].n) == 0) {
             memset(c, 0, sizeof(*c));
             c->vocab = D[i].vocab; c->hidden = D[i].hidden; c->layers = D[i].layers; c->heads = D[i].heads;
-            c->head_dim = 128; c->inter = D[i].inter; c->pos_buckets = 256; c->max_rel_pos = 512;
+            c->head_dim = D[i].hd; c->inter = D[i].inter; c->pos_buckets = 256; c->max_rel_pos = 512;
             c->pad_id = 0; c->cls_id = 1; c->sep_id = 2;
             c->class_token_index = c->vocab - 2; c->text_token_index = c->vocab - 1;
             c->pooling = GLC_POOL_LAST; c->scorer = GLC_SCORER_DOT; c->embed_class_token = 1; c->normalize_features = 0;
             c->backbone = GLC_BACKBONE_DECODER; c->kv_heads = D[i].kv; c->causal = 1; c->rope_theta = 1.0e6f;
             c->ln_eps = 1e-6f; c->logit_scale = 1.0f;
+            c->qk_norm = D[i].qkn; c->attn_bias = D[i].ab;
             return 0;
         }
     /* ModernBERT backbones (config.py CONFIGS "mb-tiny", "mb-mini", "modernbert-base", "modernbert-large") */
@@ -88,7 +93,7 @@ int glc_named_config(const char* name, glc_model_config* c) {
             c->pooling = MB[i].pooling; c->scorer = GLC_SCORER_DOT; c->embed_class_token = 1; c->normalize_features = 0;
             c->backbone = GLC_BACKBONE_MODERNBERT; c->kv_heads = c->heads; c->causal = 0; c->rope_theta = 160000.0f;
             c->ln_eps = 1e-5f; c->logit_scale = 1.0f;
-            c->local_window = MB[i].window; c->global_every = 3; c->rope_theta_local = 10000.0f;
+            c->local_window = MB[i].window; c->global_every = 3; c->rope_theta_local = 10000.0f; c->attn_bias = 1;
             return 0;
         }
     return -1;
@@ -172,15 +177,21 @@ int glc_tensor_spec(const glc_model_config* c, int i, char* name, uint64_t shape
     if (c->backbone == GLC_BACKBONE_DECODER) {
         const uint64_t nqd = (uint64_t)c->heads * (uint64_t)c->head_dim;
         const uint64_t nkvd = (uint64_t)(c->kv_heads > 0 ? c->kv_heads : c->heads) * (uint64_t)c->head_dim;
-        const int nl = GLC_DEC_TENSORS_PER_LAYER * c->layers;
+        const int per = glc_dec_tensors_per_layer(c), nl = per * c->layers;
         char buf[96];
         if (i == 0) SPEC2("embed_tokens.weight", (uint64_t)c->vocab, H, 1.0);
         if (i >= 1 && i < 1 + nl) {
-            const int l = (i - 1) / GLC_DEC_TENSORS_PER_LAYER, k = (i - 1) % GLC_DEC_TENSORS_PER_LAYER;
-            static const char* sfx[12] = {
+            /* the layer's tensors in the Qwen2 numbering (k below), without the three biases when !attn_bias; q_norm / k_norm are 12 and 13 */
+            const int l = (i - 1) / per, j = (i - 1) % per, nproj = c->attn_bias ? 7 : 4;
+            int k;
+            if (j < nproj) k = c->attn_bias ? j : (j == 0 ? 0 : 2 * j - 1);
+            else if (c->qk_norm && j < nproj + 2) k = 12 + (j - nproj);
+            else k = 7 + (j - nproj - (c->qk_norm ? 2 : 0));
+            static const char* sfx[14] = {
                 "input_layernorm.weight", "self_attn.q_proj.weight", "self_attn.q_proj.bias", "self_attn.k_proj.weight",
                 "self_attn.k_proj.bias", "self_attn.v_proj.weight", "self_attn.v_proj.bias", "self_attn.o_proj.weight",
-                "post_attention_layernorm.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight"};
+                "post_attention_layernorm.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight",
+                "self_attn.q_norm.weight", "self_attn.k_norm.weight"};
             snprintf(buf, sizeof buf, "layers.%d.%s", l, sfx[k]);
             switch (k) {
                 case 0: case 8: SPEC1(buf, H, 0.2, 1.0);
@@ -191,6 +202,8 @@ int glc_tensor_spec(const glc_model_config* c, int i, char* name, uint64_t shape
                 case 5: SPEC2(buf, nkvd, H, lin_amp(1.0, (double)H));
                 case 7: SPEC2(buf, H, nqd, lin_amp(0.7, (double)nqd));
                 case 9: case 10: SPEC2(buf, I, H, lin_amp(1.0, (double)H));
+                case 12: SPEC1(buf, (uint64_t)c->head_dim, 0.4, 1.1);       /* weights.py: q and k gains drawn differently */
+                case 13: SPEC1(buf, (uint64_t)c->head_dim, 0.3, 0.9);
                 default: SPEC2(buf, H, I, lin_amp(0.7, (double)I));
             }
         }
@@ -303,14 +316,20 @@ static int load_blob(const char* path, glc_weights* w) {
     c->embed_class_token = ints[15]; c->normalize_features = ints[16];
     c->backbone = ints[17]; c->kv_heads = ints[18]; c->causal = ints[19];
     c->ln_eps = fl[0]; c->logit_scale = fl[1]; c->rope_theta = fl[2];
-    if (ver == 3) {          /* written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
+    c->qk_norm = 0; c->attn_bias = 1;         /* what every blob older than version 4 means */
+    if (ver == 3 || ver == 4) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
         int32_t i3[2];
         float f3;
         memcpy(i3, b + 16 + sizeof ints + sizeof fl, sizeof i3);
         memcpy(&f3, b + 16 + sizeof ints + sizeof fl + sizeof i3, sizeof f3);
         c->local_window = i3[0]; c->global_every = i3[1]; c->rope_theta_local = f3;
+        if (ver == 4) {      /* Llama / Qwen3 decoders: + qk_norm, attn_bias */
+            int32_t i4[2];
+            memcpy(i4, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3, sizeof i4);
+            c->qk_norm = i4[0]; c->attn_bias = i4[1];
+        }
     }
-    if ((ver != 2 && ver != 3) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
+    if ((ver != 2 && ver != 3 && ver != 4) || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
         fprintf(stderr, "Error: '%s': unsupported GLCW header (version %u, %u tensors)\n", path, ver, nt);
         return -1;
     }

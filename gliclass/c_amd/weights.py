@@ -30,6 +30,8 @@ _F32_FIELDS = ["ln_eps", "logit_scale", "rope_theta"]
 # version 3 (ModernBERT backbone only): + local_window, global_every (int32), rope_theta_local (f32) after the v2 slots
 _V3_INT_FIELDS = ["local_window", "global_every"]
 _V3_F32_FIELDS = ["rope_theta_local"]
+# version 4 (decoder backbones other than Qwen2, i.e. (qk_norm, attn_bias) != (0, 1)): + qk_norm, attn_bias (int32) after the v3 slots
+_V4_INT_FIELDS = ["qk_norm", "attn_bias"]
 
 
 def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float, float]]:
@@ -90,19 +92,21 @@ def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float,
         return specs + head_specs()
 
     if cfg.backbone == BACKBONE_DECODER:
-        # HF Qwen2Model.state_dict() names (prefix-free).  q/k amplitudes give score std ~ 2-3 after 1/sqrt(d).
+        # HF Qwen2Model / LlamaModel / Qwen3Model.state_dict() names (prefix-free).  q/k amplitudes give score std ~ 2-3 after 1/sqrt(d).
+        # Qwen3's q_norm / k_norm gains: drawn around 1 like the other norm gains, with a wider spread and another centre for q (1.1 +- 0.4)
+        # than for k (0.9 +- 0.3), so that a skipped, swapped or mis-indexed gain is visible in the output.
         nqd, nkvd = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
         specs = [("embed_tokens.weight", (cfg.vocab, H), 1.0, 0.0)]
         for i in range(L):
             p = f"layers.{i}."
+            specs += [(p + "input_layernorm.weight", (H,), 0.2, 1.0)]
+            for nm, rows, t in (("q", nqd, 1.6), ("k", nkvd, 1.6), ("v", nkvd, 1.0)):
+                specs += [(p + f"self_attn.{nm}_proj.weight", (rows, H), lin(t, H), 0.0)]
+                if cfg.attn_bias:
+                    specs += [(p + f"self_attn.{nm}_proj.bias", (rows,), 0.1, 0.0)]
+            if cfg.qk_norm:
+                specs += [(p + "self_attn.q_norm.weight", (cfg.head_dim,), 0.4, 1.1), (p + "self_attn.k_norm.weight", (cfg.head_dim,), 0.3, 0.9)]
             specs += [
-                (p + "input_layernorm.weight", (H,), 0.2, 1.0),
-                (p + "self_attn.q_proj.weight", (nqd, H), lin(1.6, H), 0.0),
-                (p + "self_attn.q_proj.bias", (nqd,), 0.1, 0.0),
-                (p + "self_attn.k_proj.weight", (nkvd, H), lin(1.6, H), 0.0),
-                (p + "self_attn.k_proj.bias", (nkvd,), 0.1, 0.0),
-                (p + "self_attn.v_proj.weight", (nkvd, H), lin(1.0, H), 0.0),
-                (p + "self_attn.v_proj.bias", (nkvd,), 0.1, 0.0),
                 (p + "self_attn.o_proj.weight", (H, nqd), lin(0.7, nqd), 0.0),
                 (p + "post_attention_layernorm.weight", (H,), 0.2, 1.0),
                 (p + "mlp.gate_proj.weight", (I, H), lin(1.0, H), 0.0),
@@ -153,13 +157,16 @@ def make_weights(cfg: GLiClassConfig, seed: int = 42) -> Dict[str, np.ndarray]:
 
 def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
     d = cfg.asdict()
+    v4 = (cfg.qk_norm, cfg.attn_bias) != (0, 1)       # Llama / Qwen3 decoders; v4 carries the v3 slots too
     v3 = cfg.backbone == BACKBONE_MODERNBERT          # every other backbone keeps writing byte-identical v2 headers
-    b = MAGIC + struct.pack("<II", 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
+    b = MAGIC + struct.pack("<II", 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
     b += struct.pack("<%di" % len(_INT_FIELDS), *[int(d[k]) for k in _INT_FIELDS])
     b += struct.pack("<%df" % len(_F32_FIELDS), *[float(d[k]) for k in _F32_FIELDS])
-    if v3:
+    if v3 or v4:
         b += struct.pack("<%di" % len(_V3_INT_FIELDS), *[int(d[k]) for k in _V3_INT_FIELDS])
         b += struct.pack("<%df" % len(_V3_F32_FIELDS), *[float(d[k]) for k in _V3_F32_FIELDS])
+    if v4:
+        b += struct.pack("<%di" % len(_V4_INT_FIELDS), *[int(d[k]) for k in _V4_INT_FIELDS])
     assert len(b) <= HEADER_BYTES
     return b + b"\x00" * (HEADER_BYTES - len(b))
 
@@ -197,16 +204,19 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if hdr[:8] != MAGIC:
         raise ValueError("not a GLCW blob")
     ver, n_t = struct.unpack_from("<II", hdr, 8)
-    if ver not in (2, 3):
+    if ver not in (2, 3, 4):
         raise ValueError(f"unsupported GLCW version {ver}")
     ints = struct.unpack_from("<%di" % len(_INT_FIELDS), hdr, 16)
     flts = struct.unpack_from("<%df" % len(_F32_FIELDS), hdr, 16 + 4 * len(_INT_FIELDS))
     kw = dict(zip(_INT_FIELDS, ints))
     kw.update(dict(zip(_F32_FIELDS, flts)))
-    if ver == 3:
+    if ver >= 3:
         o3 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS))
         kw.update(dict(zip(_V3_INT_FIELDS, struct.unpack_from("<%di" % len(_V3_INT_FIELDS), hdr, o3))))
         kw.update(dict(zip(_V3_F32_FIELDS, struct.unpack_from("<%df" % len(_V3_F32_FIELDS), hdr, o3 + 4 * len(_V3_INT_FIELDS)))))
+    if ver >= 4:          # older blobs mean (qk_norm, attn_bias) = (0, 1), the dataclass defaults
+        o4 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS))
+        kw.update(dict(zip(_V4_INT_FIELDS, struct.unpack_from("<%di" % len(_V4_INT_FIELDS), hdr, o4))))
     cfg = GLiClassConfig(name="blob", **kw)
     tensors = {}
     for i in range(n_t):

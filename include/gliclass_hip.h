@@ -35,8 +35,8 @@ enum { GLC_POOL_FIRST = 0, GLC_POOL_AVG = 1, GLC_POOL_LAST = 2 /* last attended 
  * out_mlp = Linear(3H,4H) -> ReLU -> Linear(4H,1); 'mlp' = Linear(2H,256) -> ReLU -> Linear(256,128) -> ReLU -> Linear(128,1) on [text, class] */
 enum { GLC_SCORER_DOT = 0, GLC_SCORER_WEIGHTED_DOT = 1, GLC_SCORER_MLP = 2 };
 #define GLC_SCORER_MLP_HIDDEN 256
-/* backbone family: DeBERTa-v2/v3 disentangled encoder, or a decoder-style stack with Qwen2 arithmetic (RMSNorm, RoPE,
- * grouped-query attention, SwiGLU; SURVEY.md §8a row a16, BASELINE.json configs[4]) */
+/* backbone family: DeBERTa-v2/v3 disentangled encoder, or a decoder-style stack with Qwen2 / Llama / Qwen3 arithmetic (RMSNorm, RoPE,
+ * grouped-query attention, SwiGLU; SURVEY.md §8a row a16, BASELINE.json configs[4]; glc_model_config qk_norm / attn_bias tell the three apart) */
 enum { GLC_BACKBONE_DEBERTA = 0, GLC_BACKBONE_DECODER = 1,
        GLC_BACKBONE_MODERNBERT = 2 /* ModernBERT encoder: LayerNorm without bias, RoPE, bidirectional attention with a sliding window on the
                                       local layers, GeGLU (transformers models/modernbert/modeling_modernbert.py) */ };
@@ -53,6 +53,9 @@ typedef struct glc_model_config {
      * l % global_every == 0; rope_theta_local is the local layers' RoPE base */
     int32_t local_window, global_every;
     float rope_theta_local;
+    /* decoder backbone: qk_norm = 1 applies an RMSNorm over head_dim (gains q_norm / k_norm, epsilon ln_eps) to every query and key head
+     * before RoPE (Qwen3); attn_bias = 0 drops the q / k / v projection biases (Llama, Qwen3).  Qwen2 is (0, 1), and so is every other backbone. */
+    int32_t qk_norm, attn_bias;
 } glc_model_config;
 
 /* Tensor order expected in `tensors[]` (all fp32, row-major, nn.Linear weights are [out,in]):
@@ -70,13 +73,16 @@ typedef struct glc_model_config {
 #define GLC_TENSORS_HEAD 8
 static inline int glc_num_tensors(int layers) { return GLC_TENSORS_FIXED + GLC_TENSORS_PER_LAYER * layers + GLC_TENSORS_HEAD; }
 static inline int glc_num_scorer_tensors(int scorer) { return scorer == GLC_SCORER_WEIGHTED_DOT ? 8 : scorer == GLC_SCORER_MLP ? 6 : 0; }
-/* Decoder backbone (names of HF Qwen2Model.state_dict()):
+/* Decoder backbone (names of HF Qwen2Model / LlamaModel / Qwen3Model.state_dict()):
  *   0 embed_tokens.weight [vocab,H]
- *   1+12*l .. : layer l: input_layernorm.weight  q_proj.{w,b} [nq*d,H]  k_proj.{w,b} [nkv*d,H]  v_proj.{w,b}
- *                        o_proj.weight [H,nq*d]  post_attention_layernorm.weight
- *                        mlp.gate_proj.weight [I,H]  mlp.up_proj.weight [I,H]  mlp.down_proj.weight [H,I]
+ *   1+n*l .. : layer l: input_layernorm.weight  q_proj.weight [nq*d,H] (q_proj.bias)  k_proj.weight [nkv*d,H] (k_proj.bias)
+ *                       v_proj.weight (v_proj.bias)  [self_attn.q_norm.weight [d]  self_attn.k_norm.weight [d]]
+ *                       o_proj.weight [H,nq*d]  post_attention_layernorm.weight
+ *                       mlp.gate_proj.weight [I,H]  mlp.up_proj.weight [I,H]  mlp.down_proj.weight [H,I]
+ *     (...) only with attn_bias, [...] only with qk_norm; n = glc_dec_tensors_per_layer: 12 for Qwen2, 9 for Llama, 11 for Qwen3
  *   then norm.weight [H], then the same 8 head tensors */
 #define GLC_DEC_TENSORS_PER_LAYER 12
+static inline int glc_dec_tensors_per_layer(const glc_model_config* c) { return GLC_DEC_TENSORS_PER_LAYER - (c->attn_bias ? 0 : 3) + (c->qk_norm ? 2 : 0); }
 /* ModernBERT backbone (names of HF ModernBertModel.state_dict(); no biases anywhere):
  *   0 embeddings.tok_embeddings.weight [vocab,H]       1 embeddings.norm.weight [H]
  *   then per layer l: layers.l.attn_norm.weight [H] (only for l > 0; layer 0's is the identity)
@@ -87,7 +93,7 @@ static inline int glc_num_scorer_tensors(int scorer) { return scorer == GLC_SCOR
 static inline int glc_num_tensors_cfg(const glc_model_config* c) {
     if (c->backbone == GLC_BACKBONE_MODERNBERT)
         return 3 + GLC_MB_TENSORS_PER_LAYER * c->layers - (c->layers > 0 ? 1 : 0) + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
-    return (c->backbone == GLC_BACKBONE_DECODER ? 2 + GLC_DEC_TENSORS_PER_LAYER * c->layers + GLC_TENSORS_HEAD : glc_num_tensors(c->layers)) +
+    return (c->backbone == GLC_BACKBONE_DECODER ? 2 + glc_dec_tensors_per_layer(c) * c->layers + GLC_TENSORS_HEAD : glc_num_tensors(c->layers)) +
            glc_num_scorer_tensors(c->scorer);
 }
 /* index of layer l's first tensor (attn_norm for l > 0, Wqkv for l = 0) in the ModernBERT order */
@@ -178,6 +184,7 @@ int glc_debug_last_forward_group_split(const glc_engine* e);
 int glc_debug_set_mx(glc_engine* e, int on);
 int glc_debug_last_forward_mx(const glc_engine* e);
 int glc_debug_last_forward_mx_attention(const glc_engine* e);   /* 1: the last forward's attention ran on MX tiles (two MFMA times per product) */
+int glc_debug_last_forward_rope_epilogue(const glc_engine* e);  /* 1: (decoder) its QKV projections ran RoPE + MX tiles as their epilogue (EPI_QKVR): never with qk_norm */
 int glc_debug_set_mx_attention(glc_engine* e, int on);                 /* MX pipeline: attention on MX tiles (default) / on split-f16 units */
 long long glc_debug_mx_weight_bytes(const glc_engine* e);  /* bytes of the GX weight copies (0 until a forward has taken the MX pipeline: they are built then) */
 /* Developer: stop forwards after a stage (engine.hip) and read workspace rows decoded to fp32 (engine_debug.hip). */
