@@ -462,11 +462,14 @@ template <typename T> struct GqaFrag<true, T> { typedef f16x8s type; };
 // SPLIT (T = float): operands are split-f16 units, every product is three f16 MFMAs (glc_common.h), the probabilities are split on
 // the fly; one wave per SIMD (the doubled fragment sets need > 256 registers at D = 128).
 // WIN: sliding window of half-width `win` (keys with |q - k| > win masked), see above; WIN = false ignores `win`.
+// tile_flag (pruned last layer, engine.hip): one byte per 32-query tile [B, Sp / 32]; a wave whose tile is unflagged returns at once — no
+// load, no store: nobody reads its context rows.  Null = every tile, as before: a wave-uniform branch on the pointer, not a template parameter.
 template <typename T, int D, bool SPLIT = false, bool WIN = false>
 __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const T* __restrict__ Qf, const T* __restrict__ Kf, const T* __restrict__ Vt,
                                                                const float* __restrict__ kbias, const int* __restrict__ klen,
                                                                const int* __restrict__ kfirst_, T* __restrict__ CTX, int B, int Sp, int nq,
-                                                               int nkv, int causal, int ctx_gs, unsigned* gx_sat, int act_sc, int win = 0) {
+                                                               int nkv, int causal, int ctx_gs, unsigned* gx_sat, int act_sc, int win = 0,
+                                                               const unsigned char* __restrict__ tile_flag = nullptr) {
     static_assert(!SPLIT || sizeof(T) == 4, "split units live in the fp32 layouts");
     typedef typename GqaFrag<SPLIT, T>::type frag_t;
     constexpr int NS = D / 16, ND = D / 32;
@@ -484,6 +487,7 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
     // edge tiles of a sequence): ascending order, so that the waves of a block and consecutive blocks share most of their key tiles in L2
     const int qt = WIN ? (rem % nqb) * 4 + wave : nt - 1 - ((rem % nqb) * 4 + wave);
     if (qt < 0 || (WIN && qt >= nt)) return;
+    if (tile_flag && !tile_flag[(size_t)b * nt + qt]) return;           // pruned last layer: no selected row in this query tile
     const int q0 = qt * 32;
 
     const T* __restrict__ Qp = Qf + (((size_t)(b * nq + hq) * nt + qt) * NS) * 512 + lane * 8;
@@ -655,16 +659,17 @@ template <typename T, bool SPLIT = false> const char* launch_layout_t(hipStream_
     return nullptr;
 }
 template <typename T, bool SPLIT = false> const char* launch_gqa_t(hipStream_t st, const void* Qf, const void* Kf, const void* Vt, const float* kbias, const int* klen,
-                                               const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0, int window = 0) {
+                                               const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0, int window = 0,
+                                               const unsigned char* tile_flag = nullptr) {
     const int nt = Sp / 32, nqb = (nt + 3) / 4, per = (nq / nkv) * nqb, bg8 = (B * nkv + 7) / 8 * 8;
     const dim3 grid(per * bg8), block(256);
     if (window > 0) {           // sliding window (ModernBERT, head_dim 64, bidirectional)
         if (d != 64 || causal) return "attention_gqa_mfma: the windowed kernel takes head_dim 64 and no causal mask";
-        hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, (unsigned*)nullptr, 0, window);
+        hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, (unsigned*)nullptr, 0, window, tile_flag);
         return nullptr;
     }
-    if (d == 128) hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 128, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc());
-    else hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc());
+    if (d == 128) hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 128, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc(), 0, tile_flag);
+    else hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc(), 0, tile_flag);
     return nullptr;
 }
 
@@ -685,12 +690,12 @@ const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, co
 // MFMA grouped-query attention on the fragment-major operands written by glc_launch_qkv_layout.  CTX [B*Sp, nq*d] row-major.
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs,
-                                          int window) {
+                                          int window, const unsigned char* tile_flag) {
     if (!Qf || !Kf || !Vt || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv ||
         (d != 64 && d != 128) || window < 0 || (window > 0 && ctx_gs == 2))
         return "attention_gqa_mfma: bad args";
-    if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window);
-    if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window);
-    if (dtype == GLC_DT_F32) return launch_gqa_t<float, true>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, ctx_gs, window);   // split-f16 units
+    if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag);
+    if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag);
+    if (dtype == GLC_DT_F32) return launch_gqa_t<float, true>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, ctx_gs, window, tile_flag);   // split-f16 units
     return "attention_gqa_mfma: bad dtype";
 }

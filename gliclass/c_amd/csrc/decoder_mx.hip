@@ -100,10 +100,13 @@ __global__ __launch_bounds__(256) void qkv_layout_mx_kernel(const float* __restr
 
 // Two waves per SIMD: the operand sets of head_dim 128 (Q 64, K 64, O^T 64 registers, V^T 16 per sub-tile, read where it is used) fit 256
 // registers — the split-unit kernel, with three fragment sets of twice the size, runs one.
+// tile_flag (pruned last layer; decoder.hip attn_gqa_mfma_kernel): a wave whose query tile is unflagged returns at once; null = every
+// tile (a wave-uniform branch on the pointer).
 template <int D>
 __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char* __restrict__ Qm, const unsigned char* __restrict__ Km, const unsigned char* __restrict__ Vm,
                                                              const float* __restrict__ kbias, const int* __restrict__ klen, const int* __restrict__ kfirst_,
-                                                             unsigned char* __restrict__ CTX, int B, int Sp, int nq, int nkv, int causal, unsigned* gx_sat, int act_sc) {
+                                                             unsigned char* __restrict__ CTX, int B, int Sp, int nq, int nkv, int causal, unsigned* gx_sat, int act_sc,
+                                                             const unsigned char* __restrict__ tile_flag) {
     constexpr int NS = D / 16, NM = D / 32, ND = D / 32, TILE = 32 * D * 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
     const int hq = g * grp + rem / nqb;
     const int qt = nt - 1 - ((rem % nqb) * 4 + wave);       // longest tiles first within a head
     if (qt < 0) return;
+    if (tile_flag && !tile_flag[(size_t)b * nt + qt]) return;           // pruned last layer: no selected row in this query tile
     const int q0 = qt * 32;
 
     const unsigned char* __restrict__ Qp = Qm + ((size_t)(b * nq + hq) * nt + qt) * TILE;
@@ -274,6 +278,9 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
 // wave waits for its own pieces right before barrier(t + 1), which publishes them.  Causal: a wave's query tile ends the walk at its own
 // diagonal; waves that are done (or have no tile, or a padding-only one) keep moving their pieces and meeting the barriers until the
 // workgroup's longest walk ends.  MX steps land re-arranged as [64 lanes x first 16 B | 64 lanes x second] (per-lane DMA source address).
+// tile_flag (pruned last layer; decoder.hip attn_gqa_mfma_kernel): a workgroup none of whose four query tiles is flagged returns before
+// its first barrier; in a workgroup with some, a wave with an unflagged tile is one more wave without a walk (no Q load, no store).  Null =
+// every tile: a wave-uniform branch on the pointer.
 extern __shared__ __attribute__((aligned(16))) unsigned char smem_dmx[];
 
 __device__ __forceinline__ void glds16_sv(const unsigned char* ubase, unsigned lane_off, void* l) {      // attention_wg.hip
@@ -284,7 +291,8 @@ __device__ __forceinline__ void glds16_sv(const unsigned char* ubase, unsigned l
 template <int D>
 __global__ __launch_bounds__(256, 2) void attn_gqa_mx_ring_kernel(const unsigned char* __restrict__ Qm, const unsigned char* __restrict__ Km, const unsigned char* __restrict__ Vm,
                                                                   const float* __restrict__ kbias, const int* __restrict__ klen, const int* __restrict__ kfirst_,
-                                                                  unsigned char* __restrict__ CTX, int B, int Sp, int nq, int nkv, int causal, unsigned* gx_sat, int act_sc) {
+                                                                  unsigned char* __restrict__ CTX, int B, int Sp, int nq, int nkv, int causal, unsigned* gx_sat, int act_sc,
+                                                                  const unsigned char* __restrict__ tile_flag) {
     constexpr int NS = D / 16, NM = D / 32, ND = D / 32, TILE = 32 * D * 4, P4 = D / 32;      // P4: one-KiB pieces per wave and tile of K (and of V^T)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, h = lane >> 5;
@@ -298,10 +306,19 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_ring_kernel(const unsigned
     const int hq = g * grp + rem / nqb;
     const int qt = nt - 1 - ((rem % nqb) * 4 + wave);       // longest tiles first within a head; wave 0 holds the workgroup's last query tile
     const int q0 = qt * 32;
+    bool flagged = true;
+    if (tile_flag) {                                         // pruned last layer: the four flags of this workgroup's query tiles
+        const unsigned char* tf = tile_flag + (size_t)b * nt;
+        const int qw0 = nt - 1 - (rem % nqb) * 4;            // wave 0's tile; wave w holds qw0 - w
+        bool any = false;
+        for (int w = 0; w < 4; ++w) any = any || (qw0 - w >= 0 && tf[qw0 - w]);
+        if (!any) return;                                    // (workgroup-uniform, ahead of the first barrier)
+        flagged = qt >= 0 && tf[qt];
+    }
     const int kl = klen[b];
     int nkt_len = (kl + 31) >> 5;
     nkt_len = nkt_len < 1 ? 1 : (nkt_len > nt ? nt : nkt_len);
-    const bool has_tile = qt >= 0;
+    const bool has_tile = qt >= 0 && flagged;                // (an unflagged tile: as a wave without one)
     const bool pad_only = has_tile && q0 >= kl && q0 > 0;   // padding-only query tile of a ragged batch: zeros out, no walk
     const bool active = has_tile && !pad_only;
     const int nkt = !active ? 0 : (causal && nkt_len > qt + 1 ? qt + 1 : nkt_len);       // this wave's walk
@@ -513,7 +530,7 @@ const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const floa
 
 // Grouped-query attention on those MX tiles; CTX [B*Sp, nq*d] as GX rows.
 const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const void* Km, const void* Vm, const float* kbias, const int* klen, const int* kfirst, void* CTX,
-                                        int B, int Sp, int nq, int nkv, int d, int causal) {
+                                        int B, int Sp, int nq, int nkv, int d, int causal, const unsigned char* tile_flag) {
     if (!Qm || !Km || !Vm || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv || (d != 64 && d != 128))
         return "attention_gqa_mx: bad args";
     const int nt = Sp / 32, nqb = (nt + 3) / 4, per = (nq / nkv) * nqb, bg8 = (B * nkv + 7) / 8 * 8;
@@ -525,14 +542,14 @@ const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const vo
         static std::atomic<unsigned> ok128{0}, ok64{0};
         if (d == 128) {
             if (!glc_raise_lds_limit(attn_gqa_mx_ring_kernel<128>, (int)lds, ok128)) return "attention_gqa_mx: cannot raise the dynamic LDS limit";
-            hipLaunchKernelGGL(attn_gqa_mx_ring_kernel<128>, grid, block, lds, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc());
+            hipLaunchKernelGGL(attn_gqa_mx_ring_kernel<128>, grid, block, lds, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag);
         } else {
             if (!glc_raise_lds_limit(attn_gqa_mx_ring_kernel<64>, (int)lds, ok64)) return "attention_gqa_mx: cannot raise the dynamic LDS limit";
-            hipLaunchKernelGGL(attn_gqa_mx_ring_kernel<64>, grid, block, lds, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc());
+            hipLaunchKernelGGL(attn_gqa_mx_ring_kernel<64>, grid, block, lds, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag);
         }
         return nullptr;
     }
-    if (d == 128) hipLaunchKernelGGL(attn_gqa_mx_kernel<128>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc());
-    else hipLaunchKernelGGL(attn_gqa_mx_kernel<64>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc());
+    if (d == 128) hipLaunchKernelGGL(attn_gqa_mx_kernel<128>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag);
+    else hipLaunchKernelGGL(attn_gqa_mx_kernel<64>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag);
     return nullptr;
 }

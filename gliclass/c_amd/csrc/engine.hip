@@ -230,10 +230,14 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
         if (c.scorer != GLC_SCORER_DOT && !regrow(e, e->scorer_ws, (size_t)hr * (9 * (size_t)c.hidden + 2 * GLC_SCORER_MLP_HIDDEN) * sizeof(float))) return false;
         e->capHeadRows = hr;
     }
-    if (dec) return build_rope_tables(e, Sp);
+    // compact rows of the pruned last layer (every backbone): R = B (1 + C) rows up to the 256-row grid of the small-M GEMMs; the decoder's
+    // context rows are heads * head_dim wide, which need not be the hidden size
     const int rsel = round_up(B * (1 + (C > 0 ? C : 0)), 256);
     if (rsel > e->capSel) {
-        for (void** b : {&e->Xs, &e->Qs, &e->CTXs, &e->T1s, &e->H1s}) if (!regrow(e, *b, (size_t)rsel * c.hidden * es)) return false;
+        const size_t wide = dec ? std::max((size_t)c.hidden, (size_t)c.heads * c.head_dim) : (size_t)c.hidden;
+        for (void** b : {&e->Xs, &e->CTXs, &e->T1s, &e->H1s}) if (!regrow(e, *b, (size_t)rsel * wide * es)) return false;
+        if (!dec && !regrow(e, e->Qs, (size_t)rsel * c.hidden * es)) return false;
+        if (dec && !regrow(e, e->GUs, (size_t)rsel * 2 * c.inter * es)) return false;
         if (!regrow(e, e->FFs, (size_t)rsel * c.inter * es) || !regrow(e, e->sel_b, (size_t)rsel * sizeof(int)) || !regrow(e, e->sel_q, (size_t)rsel * sizeof(int))) return false;
         e->capSel = rsel;
     }
@@ -242,6 +246,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
         if (!regrow(e, e->tile_flag, nf)) return false;
         e->capFlag = nf;
     }
+    if (dec) return build_rope_tables(e, Sp);
     return build_position_tables(e, Sp);
 }
 
@@ -507,6 +512,48 @@ bool gated_ffn(glc_engine* e, const Glu& glu, GemmArgs f1, bool gs, const GemmGs
     return true;
 }
 
+// Exact pruning of the last layer on the pre-norm backbones (decoder, ModernBERT) — the scheme of run_forward_deberta's band_sel branch.  The head
+// reads R = B (1 + C) rows: the pooled row of every sequence (position 0, or klen - 1 with 'last' pooling) and its class-token rows.  K and V
+// of the last layer are needed at every position, so its norm, QKV projection and RoPE / layout pass run on all rows as in any layer; the
+// attention runs on the 32-query tiles that hold a selected row (tile_flag, written by the row gather), and everything behind it — context
+// gather, o-projection with the compact residual, norm, gated FFN, the final norm — on the R compact rows, plain rows of T on the
+// small-M kernels.  Average pooling reads every row and keep_hidden dumps every row: never pruned.
+struct PrunedTail {
+    bool on = false;
+    int R = 0, Rpad = 0, Cc = 0;
+    const int* klen = nullptr;        // 'last' pooling: the pooled row is klen - 1
+};
+PrunedTail pruned_tail(const glc_engine* e, int B, int C) {
+    PrunedTail t;
+    const glc_model_config& c = e->cfg;
+    t.on = e->prune_last && !e->keep_hidden && (c.pooling == GLC_POOL_FIRST || c.pooling == GLC_POOL_LAST) && c.layers > 0;
+    t.Cc = C > 0 ? C : 0;
+    t.R = B * (1 + t.Cc); t.Rpad = round_up(t.R, 256);
+    t.klen = c.pooling == GLC_POOL_LAST ? e->klen : nullptr;
+    return t;
+}
+// The compact rows behind the attention: Xs = the residual rows (gathered ahead of the layer), CTXs = the context rows.  norm(src, dst, gain)
+// is the backbone's norm over R rows; the head reads H1s, the final norm of the R rows (forward_epilogue, compact).
+template <class Norm>
+bool run_pruned_tail(glc_engine* e, const PrunedTail& t, const DecLayerW& w, const Glu& glu, int NQ, const Norm& norm) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, dt = e->dtype;
+    GemmArgs o;
+    o.A = e->CTXs; o.W = w.Wo; o.bias = nullptr; o.C = e->T1s; o.resid = e->Xs; o.Mpad = t.Rpad; o.N = H; o.K = NQ;
+    KCHK(launch_gemm_auto(e, dt, EPI_RESID, o), false);
+    KCHK(norm(e->T1s, e->H1s, w.ln2), false);
+    GemmArgs f1;      // the resident [first | second] weight (interleaved rows where the full layers gate in their epilogue), the gate as a row pass
+    f1.A = e->H1s; f1.W = w.Wgu; f1.bias = nullptr; f1.C = e->GUs; f1.Mpad = t.Rpad; f1.N = 2 * I; f1.K = H;
+    KCHK(launch_gemm_auto(e, dt, EPI_BIAS, f1), false);
+    KCHK(glu.rows(e->stream, dt, e->GUs, e->FFs, (size_t)t.R, I, e->fused_swiglu ? 1 : 0), false);
+    GemmArgs f2;
+    f2.A = e->FFs; f2.W = w.Wd; f2.bias = nullptr; f2.C = e->Xs; f2.resid = e->T1s; f2.Mpad = t.Rpad; f2.N = H; f2.K = I;
+    KCHK(launch_gemm_auto(e, dt, EPI_RESID, f2), false);
+    KCHK(norm(e->Xs, e->H1s, e->final_norm), false);
+    e->last_pruned = true;
+    return true;
+}
+
 // Decoder-style backbone: one launch sequence per batch (Q2:384-398).  Pre-norm residual stream X (operand type T).
 bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
     const glc_model_config& c = e->cfg;
@@ -549,13 +596,23 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
     e->last_mx_attn = mxa;
     e->last_rope_epi = false;
     const GemmGs gemm_gs{st, mx, M};
+    const PrunedTail pt = pruned_tail(e, B, C);
+    e->last_pruned = false;
     if (rnf) {      // the embedding rows enter the pipeline: plain fp32 (X2) -> raw group-split rows (X) + statistics
         HIPCHK(hipMemcpyAsync(e->X2, e->X, (size_t)M * H * es, hipMemcpyDeviceToDevice, st), false);
         KCHK(glc_launch_rows_to_gs_rms(st, (const float*)e->X2, e->X, sX, c.ln_eps, M, H, mx ? 1 : 0), false);
     }
     for (int l = 0; l < L; ++l) {
         const DecLayerW& w = e->dlayers[l];
-        if (!rnf) { Prof p(e, PC_LN); KCHK(gs ? glc_launch_rmsnorm_gs(st, (const float*)X, e->H1, w.ln1, c.ln_eps, M, H)
+        const bool last = pt.on && l == L - 1;        // pruned: norm, QKV and RoPE on every row (K, V), attention on the flagged tiles, the rest compact
+        const unsigned char* flag = last && mfma ? e->tile_flag : nullptr;      // (the straightforward kernel runs every row)
+        if (last) {       // the rows the head reads: the residual stream as plain rows of T (the folded pipeline's raw rows come back as fp32)
+            Prof p(e, PC_LAST);
+            HIPCHK(hipMemsetAsync(e->tile_flag, 0, (size_t)Mpad >> 5, st), false);
+            KCHK(rnf ? glc_launch_gather_rows_gs(st, X, e->cls_pos, class_cap(e), (float*)e->Xs, e->sel_b, e->sel_q, e->tile_flag, B, Sp, H, pt.Cc, mx ? 1 : 0, pt.klen)
+                     : glc_launch_gather_rows(st, dt, X, e->cls_pos, class_cap(e), e->Xs, e->sel_b, e->sel_q, e->tile_flag, B, Sp, H, pt.Cc, pt.klen), false);
+        }
+        if (!rnf) { Prof p(e, last ? PC_LAST : PC_LN); KCHK(gs ? glc_launch_rmsnorm_gs(st, (const float*)X, e->H1, w.ln1, c.ln_eps, M, H)
                                     : glc_launch_rmsnorm(st, dt, X, e->H1, w.ln1, c.ln_eps, M, H), false); }                        // Q2:280
         GemmArgs g;
         g.A = e->H1; g.W = w.Wqkv; g.bias = w.bqkv; g.C = e->QKV; g.Mpad = Mpad; g.N = NQKV; g.K = H; g.gs_c_plain = 1;
@@ -570,7 +627,7 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
         const bool rope_epi = perm && mxa && !c.qk_norm;
         if (l == 0) e->last_rope_epi = rope_epi;
         if (rope_epi) { g.rope_cs = e->ropes[{Sp, c.rope_theta}]; g.qscale = qscale; g.nq = nq; g.nkv = nkv; g.Sp = Sp; g.Mvalid = M; g.Qh = e->Qh; g.Kh = e->Kh; g.Vt = e->Vt; }
-        { Prof p(e, PC_QKV);
+        { Prof p(e, last ? PC_LAST : PC_QKV);
           if (rope_epi) KCHK(gemm_gs(EPI_QKVR, g), false);
           else {
           KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);        // Q2:206-208
@@ -578,10 +635,20 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
           if (mxa) KCHK(glc_launch_qkv_layout_mx(st, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale, w.qn, w.kn, c.ln_eps), false);     // Q2:211 RoPE, MX tiles (decoder_mx.hip)
           else if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], e->Qh, e->Kh, e->Vt, B, Sp, nq, nkv, d, qscale, w.qn, w.kn, c.ln_eps), false);   // Q2:211 RoPE
           else KCHK(glc_launch_rope_qk(st, dt, e->QKV, e->ropes[{Sp, c.rope_theta}], M, Sp, nq, nkv, d, qscale, w.qn, w.kn, c.ln_eps), false); } }
-        { Prof p(e, PC_ATTN);
-          if (mxa) KCHK(glc_launch_attention_gqa_mx(st, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal), false);
-          else if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal, mx ? 2 : (gs ? 1 : 0)), false);
+        { Prof p(e, last ? PC_LAST : PC_ATTN);
+          if (mxa) KCHK(glc_launch_attention_gqa_mx(st, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal, flag), false);
+          else if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nq, nkv, d, c.causal, last ? 0 : (mx ? 2 : (gs ? 1 : 0)), 0, flag), false);
           else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nq, nkv, d, c.causal), false); }
+        if (last) {
+            { Prof p(e, PC_LAST);
+            // context rows of the selection: plain rows of T, or on MX tiles GX rows (the kernel has no other output), which the group-split gather
+            // turns into fp32 (it writes the same row lists once more)
+            KCHK(mxa ? glc_launch_gather_rows_gs(st, e->CTX, e->cls_pos, class_cap(e), (float*)e->CTXs, e->sel_b, e->sel_q, nullptr, B, Sp, NQ, pt.Cc, 1, pt.klen)
+                     : glc_launch_gather_sel(st, dt, e->CTX, e->sel_b, e->sel_q, e->CTXs, pt.R, Sp, NQ), false);
+            auto norm = [&](const void* src, void* dst, const float* gain) { return glc_launch_rmsnorm(st, dt, src, dst, gain, c.ln_eps, pt.R, H); };
+            if (!run_pruned_tail(e, pt, w, kSwiGlu, NQ, norm)) return false; }                                                   // Q2:233-398 on R rows
+            return forward_epilogue(e, e->H1s, true, B, S, C, d_logits);
+        }
         GemmArgs o;
         o.A = e->CTX; o.W = w.Wo; o.bias = nullptr; o.C = Xn; o.resid = X; o.Mpad = Mpad; o.N = H; o.K = NQ; o.gs_resid_plain = 1;
         if (rnf) { o.gs_resid_plain = 0; o.ln_part = e->ln_part; }        // raw group-split residual in, raw group-split sum + partials out
@@ -639,6 +706,8 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
     e->last_gs = gs;
     e->last_lnf = false; e->last_mx = false; e->last_mx_attn = false;
     const GemmGs gemm_gs{st, false, M};
+    const PrunedTail pt = pruned_tail(e, B, C);
+    e->last_pruned = false;
     auto norm = [&](const void* src, const float* gamma) -> const char* {      // H1 = LN(src) (group-split rows in the gs pipeline)
         return gs ? glc_launch_layernorm_gs(st, (const float*)src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H)
                   : glc_launch_layernorm(st, dt, src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H);
@@ -648,19 +717,33 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
         const bool glob = c.local_window <= 0 || l % (c.global_every > 0 ? c.global_every : 1) == 0;
         const int win = glob ? 0 : c.local_window;
         float* cs = e->ropes[{Sp, glob ? c.rope_theta : c.rope_theta_local}];
+        const bool last = pt.on && l == L - 1;        // pruned (see run_pruned_tail): the residual rows the head reads, then K / V on every row
+        const unsigned char* flag = last && mfma ? e->tile_flag : nullptr;
+        if (last) {
+            Prof p(e, PC_LAST);
+            HIPCHK(hipMemsetAsync(e->tile_flag, 0, (size_t)Mpad >> 5, st), false);
+            KCHK(glc_launch_gather_rows(st, dt, X, e->cls_pos, class_cap(e), e->Xs, e->sel_b, e->sel_q, e->tile_flag, B, Sp, H, pt.Cc, pt.klen), false);
+        }
         // MB:326-331: attn_norm is the identity on layer 0 (the QKV projection reads the embedding norm's rows; as group-split rows in the
         // gs pipeline, where the same norm runs once more into H1)
-        if (l > 0) { Prof p(e, PC_LN); KCHK(norm(X, w.ln1), false); }
-        else if (gs) { Prof p(e, PC_LN); KCHK(glc_launch_layernorm_gs(st, (const float*)Xn, e->H1, e->eln_g, e->zero_bias, c.ln_eps, M, H), false); }
+        if (l > 0) { Prof p(e, last ? PC_LAST : PC_LN); KCHK(norm(X, w.ln1), false); }
+        else if (gs) { Prof p(e, last ? PC_LAST : PC_LN); KCHK(glc_launch_layernorm_gs(st, (const float*)Xn, e->H1, e->eln_g, e->zero_bias, c.ln_eps, M, H), false); }
         GemmArgs g;
         g.A = (l == 0 && !gs) ? X : e->H1; g.W = w.Wqkv; g.bias = nullptr; g.C = e->QKV; g.Mpad = Mpad; g.N = 3 * H; g.K = H; g.gs_c_plain = 1;
-        { Prof p(e, PC_QKV);
+        { Prof p(e, last ? PC_LAST : PC_QKV);
           KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                                      // MB:274-279
           if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);   // MB:281-282 RoPE
           else KCHK(glc_launch_rope_qk(st, dt, e->QKV, cs, M, Sp, nh, nh, d, qscale), false); }
-        { Prof p(e, PC_ATTN);                                                                                                // MB:284-297
-          if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, gs ? 1 : 0, win), false);
+        { Prof p(e, last ? PC_LAST : PC_ATTN);                                                                                 // MB:284-297
+          if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, gs && !last ? 1 : 0, win, flag), false);
           else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nh, nh, d, 0, win), false); }
+        if (last) {
+            { Prof p(e, PC_LAST);
+            KCHK(glc_launch_gather_sel(st, dt, e->CTX, e->sel_b, e->sel_q, e->CTXs, pt.R, Sp, H), false);
+            auto norm_r = [&](const void* src, void* dst, const float* gamma) { return glc_launch_layernorm(st, dt, src, dst, gamma, e->zero_bias, c.ln_eps, pt.R, H); };
+            if (!run_pruned_tail(e, pt, w, kGeGlu, H, norm_r)) return false; }                                                  // MB:299-476 on R rows
+            return forward_epilogue(e, e->H1s, true, B, S, C, d_logits);
+        }
         GemmArgs o;
         o.A = e->CTX; o.W = w.Wo; o.bias = nullptr; o.C = Xn; o.resid = X; o.Mpad = Mpad; o.N = H; o.K = H; o.gs_resid_plain = 1;
         { Prof p(e, PC_ATTN_OUT); KCHK(gs ? gemm_gs(EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }   // MB:299, :332
@@ -704,6 +787,7 @@ bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask,
         return impl == 3 ? glc_launch_attention_wg(st, dt, aa) : glc_launch_attention(st, dt, impl, aa);
     };
     const bool prune = e->prune_last && !e->keep_hidden && c.pooling == GLC_POOL_FIRST;
+    e->last_pruned = false;
     // Group-split pipeline of the fp32 mode: the activations that feed GEMMs (X, H1, FF, CTX) are kept as [32 hi | 32 lo] f16 groups
     // (same bytes as fp32), written by their producers, so that every projection runs on the 256-tile LDS-DMA kernel with three
     // f16 MFMAs per product (gemm256s.hip, GS).  Needs the split-f16 weights and attention, the pruned last layer (its compact rows go back to plain
@@ -847,6 +931,7 @@ bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask,
         KCHK(launch_gemm_auto(e, dt, EPI_RESID, f2), false);
         KCHK(glc_launch_layernorm(st, dt, e->T1s, e->Xs, w.ln2g, w.ln2b, c.ln_eps, R, H), false);
     }
+    e->last_pruned = prune;
     return forward_epilogue(e, prune ? e->Xs : e->X, prune, B, S, C, d_logits);
 }
 
@@ -1629,6 +1714,7 @@ int glc_debug_set_precision_mask(glc_engine* e, int mask) {
 int glc_debug_set_gemm_full_lines(int on) { glc_gemm_set_full_lines(on); return 0; }
 int glc_debug_keep_hidden(glc_engine* e, int on) { if (!e) return -1; e->keep_hidden = on != 0; return 0; }
 int glc_engine_set_prune_last_layer(glc_engine* e, int on) { if (!e) return -1; e->prune_last = on != 0; return 0; }
+int glc_debug_last_forward_pruned(const glc_engine* e) { return e ? (e->last_pruned ? 1 : 0) : -1; }
 int glc_debug_set_attention_impl(glc_engine* e, int impl) {
     if (!e || impl < 0 || impl > 3) { glc_set_err("bad attention impl"); return -1; }
     e->attn_impl = impl;

@@ -65,7 +65,8 @@ struct LayerW {
 struct glc_engine {
     glc_model_config cfg{};
     int dtype = GLC_F32, device = 0, attn_impl = 0;
-    bool prune_last = true;         // last layer only on the rows the head reads (exact)
+    bool prune_last = true;         // last layer only on the rows the head reads (exact; every backbone, not with average pooling or keep_hidden)
+    bool last_pruned = false;       // the last forward ran that compact last layer
     bool w_presplit = false;        // weights of the split-f16 fp32 GEMMs are split once at load (encoder layers in fp32 mode; head projectors in every mode)
     bool dec_split = false;         // decoder backbone, fp32 mode: RoPE/layout pass writes split-f16 units, grouped-query attention on three-MFMA products
     bool attn_split = false;        // fp32 mode: band attention on split-f16 operands (three f16 MFMAs per product); GLICLASS_F32_ATTN=native turns it off
@@ -117,6 +118,7 @@ struct glc_engine {
     // workspace
     int capM = 0, capB = 0, capIds = 0, capC = 0, capHeadRows = 0, capSel = 0, capGU = 0;
     void *Xs = nullptr, *Qs = nullptr, *CTXs = nullptr, *T1s = nullptr, *H1s = nullptr, *FFs = nullptr;   // compact rows of the pruned last layer
+    void* GUs = nullptr;            // ... decoder / ModernBERT: their [first | second] rows of the gated FFN, [Rpad, 2I]
     int *sel_b = nullptr, *sel_q = nullptr;
     unsigned char* tile_flag = nullptr; size_t capFlag = 0;
     void *X = nullptr, *Qh = nullptr, *Kh = nullptr, *Vt = nullptr, *CTX = nullptr, *T1 = nullptr, *H1 = nullptr, *FF = nullptr;

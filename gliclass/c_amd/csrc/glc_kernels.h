@@ -118,7 +118,7 @@ const char* glc_launch_layernorm_gs(hipStream_t st, const float* X, void* Y, con
 const char* glc_launch_embed_gs(hipStream_t st, const int64_t* ids, const int64_t* mask, const float* table, const float* gamma,
                                 const float* beta, float eps, void* X, float* kbias, int B, int S, int Sp, int H, int vocab, int pad_id, int gx = 0);
 const char* glc_launch_gather_rows_gs(hipStream_t st, const void* X, const int* cls_pos, int c_cap, float* Xs, int* sel_b, int* sel_q,
-                                      unsigned char* tile_flag, int B, int Sp, int H, int C, int gx = 0);
+                                      unsigned char* tile_flag, int B, int Sp, int H, int C, int gx = 0, const int* klen = nullptr);   // klen: as glc_launch_gather_rows
 // 256x256 LDS-DMA GEMM on GS operands (gemm256s.hip): A [Mpad, K] and W [N, K] in the GS format; three f16 MFMAs per product
 // (a_lo*w_hi + a_hi*w_lo + a_hi*w_hi) on the 16-bit kernel's ring, every 64-byte part fetched once.  EPI_GELU / EPI_BIAS: C in the GS format;
 // EPI_RESID: resid in the GS format, C plain fp32 (the LayerNorm input); EPI_QKV: Q / K / V^T as split-f16 units (qkv_split).
@@ -239,8 +239,9 @@ const char* glc_launch_l2norm_rows(hipStream_t st, float* X, int rows, int H);
 
 // Pruned last layer: compact the rows the head reads. Row r < B: [CLS] of sequence r; row B + b*C + j: class
 // token j of sequence b (sequence start if absent). Writes Xs[r,:] = X[row,:] and the (sequence, position) lists.
+// klen given ('last' pooling): row r < B is the last attended token of sequence r (klen[r] - 1; 0 for an empty row), as glc_launch_head_gather.
 const char* glc_launch_gather_rows(hipStream_t st, int dtype, const void* X, const int* cls_pos, int c_cap, void* Xs,
-                                   int* sel_b, int* sel_q, unsigned char* tile_flag, int B, int Sp, int H, int C);
+                                   int* sel_b, int* sel_q, unsigned char* tile_flag, int B, int Sp, int H, int C, const int* klen = nullptr);
 // dst[r,:] = src[(sel_b[r]*Sp + sel_q[r]),:] for r < R
 const char* glc_launch_gather_sel(hipStream_t st, int dtype, const void* src, const int* sel_b, const int* sel_q, void* dst, int R, int Sp, int H);
 // Head gather from the compact rows: Gt[b] = Xs[b]; Gc[b*C+j] = Xs[B+b*C+j] or 0 when the class token is absent.
@@ -273,16 +274,19 @@ const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const 
 const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, const float* cs, void* Qf, void* Kf, void* Vt, int B, int Sp,
                                   int nq, int nkv, int d, float qscale, const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
 // ctx_gs (fp32 mode only): write the context rows in the group-split format
+// tile_flag (here and glc_launch_attention_gqa_mx; pruned last layer): [B, Sp / 32] bytes, only the flagged 32-query tiles are computed
+// and stored, the context rows of the others keep what they held; null = every tile
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0,
-                                          int window = 0);   // window > 0 (head_dim 64, not causal, ctx_gs != 2): keys |q - k| <= window only
+                                          int window = 0,    // window > 0 (head_dim 64, not causal, ctx_gs != 2): keys |q - k| <= window only
+                                          const unsigned char* tile_flag = nullptr);
 
 // MX pipeline (decoder_mx.hip, round 4): the fused fp32 projection -> RoPE + scale + MX tiles (f16 hi units + fp8 steps, 4 bytes per element),
 // and the grouped-query attention on them (a_hi*b_hi in f16 MFMAs + both cross terms in one block-scaled fp8 MFMA); CTX as GX rows
 const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const float* cs, void* Qm, void* Km, void* Vm, int B, int Sp, int nq, int nkv, int d, float qscale,
                                      const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
 const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const void* Km, const void* Vm, const float* kbias, const int* klen, const int* kfirst, void* CTX,
-                                        int B, int Sp, int nq, int nkv, int d, int causal);
+                                        int B, int Sp, int nq, int nkv, int d, int causal, const unsigned char* tile_flag = nullptr);
 
 // dtype conversion fp32 -> T (weights upload), n elements
 const char* glc_launch_convert(hipStream_t st, int dtype, const float* src, void* dst, size_t n);

@@ -176,12 +176,14 @@ __global__ __launch_bounds__(256) void embed_gs_kernel(const int64_t* __restrict
 template <bool GX>
 __global__ __launch_bounds__(256) void gather_rows_gs_kernel(const f16_t* __restrict__ X, const int* __restrict__ cls_pos, int c_cap,
                                                              float* __restrict__ Xs, int* __restrict__ sel_b, int* __restrict__ sel_q,
-                                                             unsigned char* __restrict__ tile_flag, int B, int Sp, int H, int C, int act_sc) {
+                                                             unsigned char* __restrict__ tile_flag, int B, int Sp, int H, int C, int act_sc,
+                                                             const int* __restrict__ klen) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= B * (1 + C)) return;
     const int lane = threadIdx.x & 63;
     int b = r, pos = 0;
-    if (r >= B) {
+    if (r < B) { if (klen) pos = klen[r] > 0 ? klen[r] - 1 : 0; }      // 'last' pooling (head_gather_kernel)
+    else {
         const int rr = r - B, j = rr % C;
         b = rr / C;
         pos = j < c_cap ? cls_pos[(size_t)b * c_cap + j] : -1;
@@ -312,12 +314,14 @@ __global__ __launch_bounds__(256) void pool_avg_kernel(const T* __restrict__ X, 
 template <typename T>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const T* __restrict__ X, const int* __restrict__ cls_pos, int c_cap,
                                                           T* __restrict__ Xs, int* __restrict__ sel_b, int* __restrict__ sel_q,
-                                                          unsigned char* __restrict__ tile_flag, int B, int Sp, int H, int C) {
+                                                          unsigned char* __restrict__ tile_flag, int B, int Sp, int H, int C,
+                                                          const int* __restrict__ klen) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= B * (1 + C)) return;
     const int lane = threadIdx.x & 63;
     int b = r, pos = 0;
-    if (r >= B) {
+    if (r < B) { if (klen) pos = klen[r] > 0 ? klen[r] - 1 : 0; }      // 'last' pooling (head_gather_kernel)
+    else {
         const int rr = r - B, j = rr % C;
         b = rr / C;
         pos = j < c_cap ? cls_pos[(size_t)b * c_cap + j] : -1;
@@ -502,11 +506,11 @@ const char* glc_launch_embed_gs(hipStream_t st, const int64_t* ids, const int64_
 }
 
 const char* glc_launch_gather_rows_gs(hipStream_t st, const void* X, const int* cls_pos, int c_cap, float* Xs, int* sel_b, int* sel_q,
-                                      unsigned char* tile_flag, int B, int Sp, int H, int C, int gx) {
+                                      unsigned char* tile_flag, int B, int Sp, int H, int C, int gx, const int* klen) {
     if (B <= 0 || C < 0 || !X || !cls_pos || !Xs || !sel_b || !sel_q || H % 32) return "gather_rows_gs: bad args";
     const int rows = B * (1 + C);
-    if (gx) hipLaunchKernelGGL(gather_rows_gs_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, (const f16_t*)X, cls_pos, c_cap, Xs, sel_b, sel_q, tile_flag, B, Sp, H, C, glc_gx_act_sc());
-    else hipLaunchKernelGGL(gather_rows_gs_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, (const f16_t*)X, cls_pos, c_cap, Xs, sel_b, sel_q, tile_flag, B, Sp, H, C, 0);
+    if (gx) hipLaunchKernelGGL(gather_rows_gs_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, (const f16_t*)X, cls_pos, c_cap, Xs, sel_b, sel_q, tile_flag, B, Sp, H, C, glc_gx_act_sc(), klen);
+    else hipLaunchKernelGGL(gather_rows_gs_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, (const f16_t*)X, cls_pos, c_cap, Xs, sel_b, sel_q, tile_flag, B, Sp, H, C, 0, klen);
     return nullptr;
 }
 
@@ -541,11 +545,11 @@ const char* glc_launch_gather_sel(hipStream_t st, int dtype, const void* src, co
 }
 
 const char* glc_launch_gather_rows(hipStream_t st, int dtype, const void* X, const int* cls_pos, int c_cap, void* Xs, int* sel_b,
-                                   int* sel_q, unsigned char* tile_flag, int B, int Sp, int H, int C) {
+                                   int* sel_q, unsigned char* tile_flag, int B, int Sp, int H, int C, const int* klen) {
     if (B <= 0 || C < 0 || !X || !cls_pos || !Xs || !sel_b || !sel_q || H % 8) return "gather_rows: bad args";
     const int rows = B * (1 + C);
     DISPATCH_T(dtype, {
-        hipLaunchKernelGGL(gather_rows_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, st, (const T*)X, cls_pos, c_cap, (T*)Xs, sel_b, sel_q, tile_flag, B, Sp, H, C);
+        hipLaunchKernelGGL(gather_rows_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, st, (const T*)X, cls_pos, c_cap, (T*)Xs, sel_b, sel_q, tile_flag, B, Sp, H, C, klen);
     });
     return nullptr;
 }

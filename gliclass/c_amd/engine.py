@@ -92,6 +92,10 @@ class Engine:
     def set_prune_last_layer(self, on=True):
         self.L.glc_engine_set_prune_last_layer(self.h, int(on))
 
+    def last_pruned(self):
+        """1: the last forward ran the compact (pruned) last layer, 0: it ran every row"""
+        return int(self.L.glc_debug_last_forward_pruned(self.h))
+
     def set_length_buckets(self, max_groups):
         if self.L.glc_engine_set_length_buckets(self.h, int(max_groups)) != 0:
             raise self._err("glc_engine_set_length_buckets")

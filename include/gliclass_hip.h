@@ -136,9 +136,12 @@ int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_ma
 int glc_engine_sync(glc_engine* e);
 int glc_engine_device_forward_valid(glc_engine* e);      /* 1 valid / 0 repeat the forward / -1 error; the stream must be idle (see above) */
 
-/* Exact last-layer pruning (default on; env GLICLASS_PRUNE_LAST=0 disables): the final encoder layer computes
- * Q / attention output / FFN only for the rows the head reads ([CLS] + class tokens).  Logits are unchanged. */
+/* Exact last-layer pruning (default on; env GLICLASS_PRUNE_LAST=0 disables), on every backbone: the final layer computes attention
+ * output, output projection and FFN (DeBERTa: Q as well) only for the rows the head reads — the pooled row of each sequence ([CLS] /
+ * position 0, or the last attended token with 'last' pooling) and its class tokens; K and V are still made for every position.  Logits
+ * are unchanged.  Never with average pooling (it reads every row) and never under glc_debug_keep_hidden (it dumps every row). */
 int glc_engine_set_prune_last_layer(glc_engine* e, int on);
+int glc_debug_last_forward_pruned(const glc_engine* e);        /* 1: the last forward ran that compact last layer, 0: it did not, -1: null engine */
 
 /* Length bucketing of glc_engine_forward (host buffers): the reference pads every row of a batch to the longest one
  * (/root/reference/src/tokenizer.c:44-54); rows are independent, so a ragged batch is run as up to `max_groups` groups of
