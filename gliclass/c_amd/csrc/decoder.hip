@@ -665,7 +665,7 @@ template <typename T, bool SPLIT = false> const char* launch_gqa_t(hipStream_t s
     const dim3 grid(per * bg8), block(256);
     if (window > 0) {           // sliding window (ModernBERT, head_dim 64, bidirectional)
         if (d != 64 || causal) return "attention_gqa_mfma: the windowed kernel takes head_dim 64 and no causal mask";
-        hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, (unsigned*)nullptr, 0, window, tile_flag);
+        hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc(), window, tile_flag);
         return nullptr;
     }
     if (d == 128) hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 128, SPLIT>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, causal, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc(), 0, tile_flag);
@@ -692,7 +692,7 @@ const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void*
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs,
                                           int window, const unsigned char* tile_flag) {
     if (!Qf || !Kf || !Vt || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv ||
-        (d != 64 && d != 128) || window < 0 || (window > 0 && ctx_gs == 2))
+        (d != 64 && d != 128) || window < 0)
         return "attention_gqa_mfma: bad args";
     if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag);
     if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag);

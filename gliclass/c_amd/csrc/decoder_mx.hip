@@ -102,11 +102,15 @@ __global__ __launch_bounds__(256) void qkv_layout_mx_kernel(const float* __restr
 // registers — the split-unit kernel, with three fragment sets of twice the size, runs one.
 // tile_flag (pruned last layer; decoder.hip attn_gqa_mfma_kernel): a wave whose query tile is unflagged returns at once; null = every
 // tile (a wave-uniform branch on the pointer).
-template <int D>
+// WIN (ModernBERT's local layers, bidirectional; decoder.hip attn_gqa_mfma_kernel<.., WIN = true>): a wave visits only the key tiles
+// floor((q0 - win) / 32) .. floor((q0 + 31 + win) / 32), clipped to the key length, and masks |q - k| > win per element on the edge tiles only
+// (a wave-uniform branch); query tiles in ascending order, so that the waves of a block share most of their few key tiles in L2.  A local
+// layer's wave walks about 2 win / 32 + 2 tiles: no K ring to amortise, hence this barrier-free form.  WIN = false ignores `win`.
+template <int D, bool WIN = false>
 __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char* __restrict__ Qm, const unsigned char* __restrict__ Km, const unsigned char* __restrict__ Vm,
                                                              const float* __restrict__ kbias, const int* __restrict__ klen, const int* __restrict__ kfirst_,
                                                              unsigned char* __restrict__ CTX, int B, int Sp, int nq, int nkv, int causal, unsigned* gx_sat, int act_sc,
-                                                             const unsigned char* __restrict__ tile_flag) {
+                                                             const unsigned char* __restrict__ tile_flag, int win = 0) {
     constexpr int NS = D / 16, NM = D / 32, ND = D / 32, TILE = 32 * D * 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
@@ -119,8 +123,8 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
     if (bg >= B * nkv) return;
     const int b = bg / nkv, g = bg - b * nkv;
     const int hq = g * grp + rem / nqb;
-    const int qt = nt - 1 - ((rem % nqb) * 4 + wave);       // longest tiles first within a head
-    if (qt < 0) return;
+    const int qt = WIN ? (rem % nqb) * 4 + wave : nt - 1 - ((rem % nqb) * 4 + wave);       // longest tiles first within a head (windowed: ascending)
+    if (qt < 0 || (WIN && qt >= nt)) return;
     if (tile_flag && !tile_flag[(size_t)b * nt + qt]) return;           // pruned last layer: no selected row in this query tile
     const int q0 = qt * 32;
 
@@ -139,6 +143,13 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
     int nkt = (klen[b] + 31) >> 5;
     nkt = nkt < 1 ? 1 : (nkt > nt ? nt : nkt);
     if (causal && nkt > qt + 1) nkt = qt + 1;
+    int kt0 = 0;                             // first key tile visited
+    if constexpr (WIN) {
+        kt0 = q0 - win > 0 ? (q0 - win) >> 5 : 0;
+        const int klast = (q0 + 31 + win) >> 5;
+        if (nkt > klast + 1) nkt = klast + 1;
+        if (kt0 > nkt - 1) kt0 = nkt - 1;    // (q0 < klen here, so kt0 <= qt < nkt already; kept as a guard)
+    }
     const int kfirst = kfirst_[b];
     const int foff = 8 * h;
 
@@ -151,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
         for (int m = 0; m < NM; ++m) x[m] = cat8(*reinterpret_cast<const i32x4*>(tile + NS * 1024 + m * 2048 + lane * 32), *reinterpret_cast<const i32x4*>(tile + NS * 1024 + m * 2048 + lane * 32 + 16));
     };
     load_tile(Qp, qf, qx);
-    load_tile(Kp, kf, kx);
+    load_tile(Kp + (size_t)kt0 * TILE, kf, kx);
     f32x16 o[ND];
 #pragma unroll
     for (int a = 0; a < ND; ++a)
@@ -161,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
     float one_f = 1.0f;
     asm volatile("" : "+s"(one_f));          // opaque to the optimiser: fma(p, 1, -half) stays a v_fma_mix_f32 (attention_mx.hip)
 
-    for (int kt = 0; kt < nkt; ++kt) {
+    for (int kt = kt0; kt < nkt; ++kt) {
         const int ktn = kt + 1 < nkt ? kt + 1 : kt;
         // S^T = K Q^T ; reg i <-> key k0 + 16*(i>>3) + 8h + (i&7), column = query c
         f32x16 sacc;
@@ -189,6 +200,15 @@ __global__ __launch_bounds__(256, 2) void attn_gqa_mx_kernel(const unsigned char
             for (int i = 0; i < 16; ++i) {
                 const int ko = 16 * (i >> 3) + foff + (i & 7);
                 if (ko > c) sv[i] = GLC_NEG_BIG;
+            }
+        }
+        if constexpr (WIN) {
+            if (q0 + 31 - k0 > win || k0 + 31 - q0 > win) {                // wave-uniform: an edge tile holds pairs beyond the window
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int dq = (q0 + c) - (k0 + 16 * (i >> 3) + foff + (i & 7));
+                    if (dq > win || -dq > win) sv[i] = GLC_NEG_BIG;
+                }
             }
         }
         float mx = fmaxf(fmaxf(sv[0], sv[1]), sv[2]);
@@ -528,14 +548,20 @@ const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const floa
     return nullptr;
 }
 
-// Grouped-query attention on those MX tiles; CTX [B*Sp, nq*d] as GX rows.
+// Grouped-query attention on those MX tiles; CTX [B*Sp, nq*d] as GX rows.  win > 0 (ModernBERT's local layers: head_dim 64, not causal): keys
+// |q - k| <= win only, on the per-wave kernel; win == 0: the K / V^T ring kernel.
 const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const void* Km, const void* Vm, const float* kbias, const int* klen, const int* kfirst, void* CTX,
-                                        int B, int Sp, int nq, int nkv, int d, int causal, const unsigned char* tile_flag) {
-    if (!Qm || !Km || !Vm || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv || (d != 64 && d != 128))
+                                        int B, int Sp, int nq, int nkv, int d, int causal, const unsigned char* tile_flag, int win) {
+    if (!Qm || !Km || !Vm || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv || (d != 64 && d != 128) || win < 0)
         return "attention_gqa_mx: bad args";
     const int nt = Sp / 32, nqb = (nt + 3) / 4, per = (nq / nkv) * nqb, bg8 = (B * nkv + 7) / 8 * 8;
     const dim3 grid(per * bg8), block(256);
     unsigned* sat = glc_gx_sat_ptr();
+    if (win > 0) {
+        if (d != 64 || causal) return "attention_gqa_mx: the windowed kernel takes head_dim 64 and no causal mask";
+        hipLaunchKernelGGL((attn_gqa_mx_kernel<64, true>), grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, 0, sat, glc_gx_act_sc(), tile_flag, win);
+        return nullptr;
+    }
     static const bool direct = glc_dev_env("GLC_DEC_ATTN_DIRECT") && atoi(glc_dev_env("GLC_DEC_ATTN_DIRECT")) != 0;      // developer A/B: K / V^T per wave from memory
     if (!direct) {
         const size_t lds = (size_t)4 * 32 * d * 4;            // K ring + V^T ring, two slots each
@@ -549,7 +575,7 @@ const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const vo
         }
         return nullptr;
     }
-    if (d == 128) hipLaunchKernelGGL(attn_gqa_mx_kernel<128>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag);
-    else hipLaunchKernelGGL(attn_gqa_mx_kernel<64>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag);
+    if (d == 128) hipLaunchKernelGGL(attn_gqa_mx_kernel<128>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag, 0);
+    else hipLaunchKernelGGL(attn_gqa_mx_kernel<64>, grid, block, 0, st, (const unsigned char*)Qm, (const unsigned char*)Km, (const unsigned char*)Vm, kbias, klen, kfirst, (unsigned char*)CTX, B, Sp, nq, nkv, causal, sat, glc_gx_act_sc(), tile_flag, 0);
     return nullptr;
 }

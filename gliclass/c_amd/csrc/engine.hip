@@ -344,6 +344,11 @@ static bool build_mx_weights_impl(glc_engine* e, std::vector<void**>& made) {
                 HIPCHK(hipMemcpyAsync(w.bqkv_p + hd * 128 + 64, w.bqkv + hd * 128 + 32, 32 * sizeof(float), hipMemcpyDeviceToDevice, e->stream), false);
             }
         }
+    } else if (c.backbone == GLC_BACKBONE_MODERNBERT) {
+        // (no norm fold on this backbone: the unfolded Wqkv / Wo / Wi / mlp.Wo; Wi keeps its interleaved 16 input / 16 gate rows)
+        for (auto& w : e->dlayers)
+            if (!copy(w.Wqkv, 3 * H * H, w.Wqkv_x, w.ws_qkv) || !copy(w.Wo, H * H, w.Wo_x, w.ws_o) ||
+                !copy(w.Wgu, 2 * I * H, w.Wgu_x, w.ws_gu) || !copy(w.Wd, H * I, w.Wd_x, w.ws_d)) return false;
     } else {
         for (size_t l = 0; l < e->layers.size(); ++l) {
             LayerW& w = e->layers[l];
@@ -679,14 +684,17 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
 
 // ModernBERT backbone (transformers models/modernbert/modeling_modernbert.py, cited as MB:<line>): one launch sequence per batch.
 // Pre-norm residual stream X (operand type T; plain fp32 rows in the fp32 mode), bias-free LayerNorms (beta = e->zero_bias),
-// bidirectional attention with RoPE, the local layers on the windowed attention kernels, GeGLU.  The MX pipeline is not built for
-// this backbone; the fp32 mode's group-split pipeline runs with the norms as kernels of their own (no fold).
+// bidirectional attention with RoPE, the local layers on the windowed attention kernels, GeGLU.  The fp32 mode's group-split pipeline
+// runs with the norms as kernels of their own (no fold).  The MX pipeline is opt-in here (glc_engine_enable_mx / GLICLASS_MX_MODERNBERT=1):
+// the same launch sequence with the norm, context and GeGLU rows as GX rows, the four projections on gemm256x (GeGLU in its epilogue) and
+// the attention on MX tiles — the ring kernel on the global layers, the windowed per-wave kernel on the local ones (decoder_mx.hip).
 bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, I = c.inter, nh = c.heads, d = c.head_dim, L = c.layers;
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     hipStream_t st = e->stream;
     const int dt = e->dtype;
+    GxScope gx_scope(e);                     // fp8 range guard + activation exponent (see run_forward_decoder)
     if (!forward_prologue(e, ids, mask, B, S)) return false;
     void *X = e->X, *Xn = e->X2;
     { Prof p(e, PC_EMBED);                                                                                                   // MB:52-71
@@ -704,12 +712,21 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
         gs = e->gs_mode == 2 || !glc_gemm_small_m(t);
     }
     e->last_gs = gs;
-    e->last_lnf = false; e->last_mx = false; e->last_mx_attn = false;
-    const GemmGs gemm_gs{st, false, M};
+    e->last_lnf = false;
+    // MX pipeline (opt-in: glc_engine_enable_mx): GX rows + gemm256x for the four projections of every layer, attention on MX tiles
+    bool mx = gs && e->mx && e->mx_built && e->fused_swiglu && e->prec_mask == 0;
+    if (mx && !build_mx_weights(e)) mx = false;          // (no copies: this and every later forward stay on the split-f16 kernels)
+    for (int l = 0; mx && l < L; ++l) mx = e->dlayers[l].Wqkv_x && e->dlayers[l].Wo_x && e->dlayers[l].Wgu_x && e->dlayers[l].Wd_x;
+    e->last_mx = mx;
+    const bool mxa = mx && e->mx_attn;       // attention on MX tiles too (decoder_mx.hip); else split-f16 units with GX context rows
+    e->last_mx_attn = mxa;
+    e->last_rope_epi = false;
+    const int gxr = mx ? 1 : 0;
+    const GemmGs gemm_gs{st, mx, M};
     const PrunedTail pt = pruned_tail(e, B, C);
     e->last_pruned = false;
-    auto norm = [&](const void* src, const float* gamma) -> const char* {      // H1 = LN(src) (group-split rows in the gs pipeline)
-        return gs ? glc_launch_layernorm_gs(st, (const float*)src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H)
+    auto norm = [&](const void* src, const float* gamma) -> const char* {      // H1 = LN(src) (group-split rows in the gs pipeline, GX rows on the MX pipeline)
+        return gs ? glc_launch_layernorm_gs(st, (const float*)src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H, gxr)
                   : glc_launch_layernorm(st, dt, src, e->H1, gamma, e->zero_bias, c.ln_eps, M, H);
     };
     for (int l = 0; l < L; ++l) {
@@ -727,33 +744,41 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
         // MB:326-331: attn_norm is the identity on layer 0 (the QKV projection reads the embedding norm's rows; as group-split rows in the
         // gs pipeline, where the same norm runs once more into H1)
         if (l > 0) { Prof p(e, last ? PC_LAST : PC_LN); KCHK(norm(X, w.ln1), false); }
-        else if (gs) { Prof p(e, last ? PC_LAST : PC_LN); KCHK(glc_launch_layernorm_gs(st, (const float*)Xn, e->H1, e->eln_g, e->zero_bias, c.ln_eps, M, H), false); }
+        else if (gs) { Prof p(e, last ? PC_LAST : PC_LN); KCHK(glc_launch_layernorm_gs(st, (const float*)Xn, e->H1, e->eln_g, e->zero_bias, c.ln_eps, M, H, gxr), false); }
         GemmArgs g;
         g.A = (l == 0 && !gs) ? X : e->H1; g.W = w.Wqkv; g.bias = nullptr; g.C = e->QKV; g.Mpad = Mpad; g.N = 3 * H; g.K = H; g.gs_c_plain = 1;
+        if (mx) { g.W = w.Wqkv_x; g.mx_ws = w.ws_qkv; }
         { Prof p(e, last ? PC_LAST : PC_QKV);
           KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                                      // MB:274-279
-          if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);   // MB:281-282 RoPE
+          if (mxa) KCHK(glc_launch_qkv_layout_mx(st, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);     // MB:281-282 RoPE, MX tiles
+          else if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);   // MB:281-282 RoPE
           else KCHK(glc_launch_rope_qk(st, dt, e->QKV, cs, M, Sp, nh, nh, d, qscale), false); }
         { Prof p(e, last ? PC_LAST : PC_ATTN);                                                                                 // MB:284-297
-          if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, gs && !last ? 1 : 0, win, flag), false);
+          if (mxa) KCHK(glc_launch_attention_gqa_mx(st, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, flag, win), false);
+          else if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, last ? 0 : (mx ? 2 : (gs ? 1 : 0)), win, flag), false);
           else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nh, nh, d, 0, win), false); }
         if (last) {
             { Prof p(e, PC_LAST);
-            KCHK(glc_launch_gather_sel(st, dt, e->CTX, e->sel_b, e->sel_q, e->CTXs, pt.R, Sp, H), false);
+            // (on MX tiles the context rows are GX rows — the kernel has no other output: the group-split gather turns the selection into fp32)
+            KCHK(mxa ? glc_launch_gather_rows_gs(st, e->CTX, e->cls_pos, class_cap(e), (float*)e->CTXs, e->sel_b, e->sel_q, nullptr, B, Sp, H, pt.Cc, 1, pt.klen)
+                     : glc_launch_gather_sel(st, dt, e->CTX, e->sel_b, e->sel_q, e->CTXs, pt.R, Sp, H), false);
             auto norm_r = [&](const void* src, void* dst, const float* gamma) { return glc_launch_layernorm(st, dt, src, dst, gamma, e->zero_bias, c.ln_eps, pt.R, H); };
             if (!run_pruned_tail(e, pt, w, kGeGlu, H, norm_r)) return false; }                                                  // MB:299-476 on R rows
             return forward_epilogue(e, e->H1s, true, B, S, C, d_logits);
         }
         GemmArgs o;
         o.A = e->CTX; o.W = w.Wo; o.bias = nullptr; o.C = Xn; o.resid = X; o.Mpad = Mpad; o.N = H; o.K = H; o.gs_resid_plain = 1;
+        if (mx) { o.W = w.Wo_x; o.mx_ws = w.ws_o; }
         { Prof p(e, PC_ATTN_OUT); KCHK(gs ? gemm_gs(EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }   // MB:299, :332
         std::swap(X, Xn);
         { Prof p(e, PC_LN); KCHK(norm(X, w.ln2), false); }                                                                  // MB:333
         GemmArgs f1;
         f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
+        if (mx) { f1.W = w.Wgu_x; f1.mx_ws = w.ws_gu; f1.glu_interleaved = 1; }      // (mx implies fused_swiglu: Wi was interleaved at upload)
         if (!gated_ffn(e, kGeGlu, f1, gs, gemm_gs, M)) return false;                                                        // MB:89-91 gelu(input) * gate
         GemmArgs f2;
         f2.A = e->FF; f2.W = w.Wd; f2.bias = nullptr; f2.C = Xn; f2.resid = X; f2.Mpad = Mpad; f2.N = H; f2.K = I; f2.gs_resid_plain = 1;
+        if (mx) { f2.W = w.Wd_x; f2.mx_ws = w.ws_d; }
         { Prof p(e, PC_FFN2); KCHK(gs ? gemm_gs(EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }
         std::swap(X, Xn);
         if (l + 1 < L && !dump_hidden(e, l + 1, X, M)) return false;
@@ -1075,6 +1100,8 @@ bool create_modernbert(glc_engine* e, const float* const* tensors, float* stagin
             return false;
         if (attn_norm && !(w.ln1 = upload_f32(e, attn_norm, H))) return false;
         if (!(w.ln2 = upload_f32(e, t[2], H))) return false;
+        // (the largest element a normalised row can hold, |gamma| sqrt(H): the rows of these norms are GX operands on the MX pipeline, glc_engine_enable_mx)
+        for (int i = 0; i < H; ++i) e->mb_ln_bound = fmaxf(e->mb_ln_bound, fmaxf(attn_norm ? fabsf(attn_norm[i]) : fabsf(tensors[1][i]), fabsf(t[2][i])) * sqrtf((float)H));
     }
     e->final_norm = upload_f32(e, tensors[L > 0 ? glc_mb_layer_base(L) : 2], H);
     return e->final_norm != nullptr;
@@ -1297,6 +1324,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     // everywhere (three f16 MFMAs per product, ~1e-5); GLICLASS_MX=build: GX weight copies built, pipeline off until glc_debug_set_mx.
     {
         const char* mv = getenv("GLICLASS_MX");
+        e->mx_env = !mv ? 0 : !strcmp(mv, "0") ? 1 : !strcmp(mv, "build") ? 2 : 0;
         const bool eligible = dec ? (dtype == GLC_F32 && e->w_presplit && e->dec_split && e->ln_fused && cfg->hidden % 256 == 0 && (2 * cfg->inter) % 256 == 0 && cfg->inter % 32 == 0)
                                   : (dtype == GLC_F32 && e->w_presplit && e->attn_split && e->ln_fused && cfg->hidden % 256 == 0 && cfg->inter % 256 == 0 && cfg->layers >= 2);
         e->mx_built = eligible && !mb && !(mv && !strcmp(mv, "0"));      // (no MX pipeline for the ModernBERT backbone)
@@ -1323,7 +1351,54 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (!e->emb || !upload_as(e, tensors[0], nemb, e->emb, staging)) return fail();
     const bool loaded = dec ? create_decoder(e, tensors, staging) : mb ? create_modernbert(e, tensors, staging) : create_deberta(e, tensors, staging);
     if (!loaded || !upload_head(e, tensors + n_tensors - GLC_TENSORS_HEAD - glc_num_scorer_tensors(cfg->scorer))) return fail();
+    // ModernBERT: the MX pipeline is opt-in; the environment makes the call glc_engine_enable_mx documents (read once, here).  An engine it does
+    // not fit stays as it is: not an error.
+    if (mb) {
+        const char* ov = getenv("GLICLASS_MX_MODERNBERT");
+        if (ov && !strcmp(ov, "1") && glc_engine_enable_mx(e) != 0)
+            fprintf(stderr, "gliclass: GLICLASS_MX_MODERNBERT=1 has no effect on this engine (%s)\n", glc_last_error());
+    }
     return e;
+}
+
+/* Opt-in MX pipeline of the ModernBERT backbone (include/gliclass_hip.h). */
+int glc_engine_enable_mx(glc_engine* e) {
+    if (!e) { glc_set_err("enable_mx: null engine"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->cfg.backbone != GLC_BACKBONE_MODERNBERT) {
+        if (e->mx_built) return 0;
+        glc_set_err("enable_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1;
+    }
+    if (e->mx_built && e->mx_ready) return 0;
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter;
+    const char* why = nullptr;
+    if (e->dtype != GLC_F32) why = "the MX pipeline runs in the fp32 mode only (this engine's dtype is 16-bit)";
+    else if (e->mx_env == 1) why = "GLICLASS_MX=0 was set when the engine was created";
+    else if (!e->w_presplit || !e->dec_split) why = "it needs the split-f16 weights and attention (GLICLASS_F32_GEMM / GLICLASS_F32_ATTN = native were set at creation)";
+    else if (c.head_dim != 64) why = "head_dim must be 64";
+    else if (H % 256) why = "the hidden size must be a multiple of 256";
+    else if ((2 * I) % 256 || I % 32) why = "twice the GeGLU width must be a multiple of 256 (modernbert-large: 2 x 2624 = 5248 is not) and the width a multiple of 32";
+    else if (!e->fused_swiglu) why = "the GeGLU epilogue is switched off for this engine";
+    else if (e->keep_hidden) why = "keep_hidden is on (the hidden-state dump needs plain rows)";
+    if (why) { glc_set_err(std::string("enable_mx: ") + why); return -1; }
+    HIPCHK(hipSetDevice(e->device), -1);
+    if (!init_range_guard(e)) return -1;
+    if (!e->splitk_ws) {                                    // (the scratch word of the weight conversion: ensure_capacity's workspace)
+        e->splitk_ws_bytes = (size_t)64 << 20;
+        e->splitk_ws = (float*)dmalloc(e, e->splitk_ws_bytes, false);
+        if (!e->splitk_ws) { e->splitk_ws_bytes = 0; return -1; }
+    }
+    e->mx_built = true;
+    if (!build_mx_weights(e)) { glc_set_err(std::string("enable_mx: the GX weight copies could not be built (") + glc_last_error() + ")"); return -1; }      // (mx_built is off again)
+    e->mx = e->mx_env != 2;                                 // GLICLASS_MX=build: copies built, pipeline off until glc_debug_set_mx
+    // Proactive activation exponent (as create_deberta): an element of a normalised row is at most |gamma| sqrt(H)
+    if (e->mb_ln_bound > 448.0f && e->act_sc == 0) {
+        e->act_sc = kActScLow;
+        fprintf(stderr, "gliclass: LayerNorm gains of this checkpoint allow activations up to %.0f (beyond the fp8 range of the MX operand images, 448); "
+                        "this engine's activation rows carry exponent %d (|x| up to %d) from the start\n", e->mb_ln_bound, kActScLow, 448 << -kActScLow);
+    }
+    return 0;
 }
 
 void glc_engine_destroy(glc_engine* e) {

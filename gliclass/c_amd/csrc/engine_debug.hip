@@ -222,12 +222,12 @@ int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r) {
     GemmArgs g;
     g.Mpad = r->Mpad; g.N = r->N; g.K = r->K; g.m_split = r->m_split; g.Mvalid = r->Mvalid; g.Sp = r->Sp; g.nh = r->nh; g.H = r->H; g.nq = r->nq; g.nkv = r->nkv;
     g.qscale = r->qscale; g.qkv_skip_q = r->qkv_skip_q; g.qkv_split = r->qkv_split; g.qkv_mxt = r->qkv_mxt; g.gs_c_plain = r->gs_c_plain; g.gs_resid_plain = r->gs_resid_plain;
-    g.perm_cols = r->perm_cols; g.prec = r->prec; g.mx_ws = r->mx_ws; g.act_sc = r->act_sc; g.gx_rows = r->gx_rows;
+    g.perm_cols = r->perm_cols; g.glu_interleaved = r->glu_interleaved; g.prec = r->prec; g.mx_ws = r->mx_ws; g.act_sc = r->act_sc; g.gx_rows = r->gx_rows;
     g.w_presplit = kern == GLC_GEMM_RUN_128 && dtype == GLC_F32 && r->w_presplit;
     g.A = encode(r->A, nA, 0, false);
     if (!msg) g.W = encode(r->W, nW, 1, false);
     if (!msg && r->W2) g.W2 = encode(r->W2, nW, 1, false);
-    if (!msg && r->resid) g.resid = encode(r->resid, nC, 0, gs && r->gs_resid_plain);
+    if (!msg && r->resid) g.resid = encode(r->resid, nC, 0, (gs || mx) && r->gs_resid_plain);
     if (msg) return fail(msg, own ? -1 : -2);      // a converter's refusal counts as the launcher's: nothing has been launched
     auto upf = [&](const float* h, size_t n) -> const float* { if (!h) return nullptr; const float* p = (const float*)bufs.up(h, n * 4); if (!p) msg = "gemm_run: upload failed"; return p; };
     g.bias = upf(r->bias, r->N); g.bias2 = upf(r->bias2, r->N); g.ln_c = upf(r->ln_c, r->N); g.r_gamma = upf(r->r_gamma, r->N); g.r_beta = upf(r->r_beta, r->N);
@@ -279,7 +279,7 @@ int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r) {
     for (int i = 0; i < 3; ++i) ok = ok && back(r->out[i], outs[i].base + RUN_GUARD, gemm_run_out_bytes(*r, dtype, i));
     if (r->want_ln_part) ok = ok && back(r->ln_part, outs[3].base + RUN_GUARD, lp_bytes);
     ok = ok && back(r->A_img, g.A, nA * es) && back(r->W_img, g.W, nW * es) && (!g.W2 || back(r->W2_img, g.W2, nW * es)) &&
-         (!g.resid || back(r->resid_img, g.resid, nC * (gs && r->gs_resid_plain ? 4 : es))) && back(r->sat, sat, 8);
+         (!g.resid || back(r->resid_img, g.resid, nC * ((gs || mx) && r->gs_resid_plain ? 4 : es))) && back(r->sat, sat, 8);
     std::vector<unsigned char> gd(RUN_GUARD);
     r->guards_ok = 1;
     r->cus = glc_device_cus();

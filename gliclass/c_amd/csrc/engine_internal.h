@@ -41,6 +41,8 @@ struct DecLayerW {                     // decoder-style backbone (decoder.hip)
     void *Wqkvf = nullptr, *Wguf = nullptr;                                   // fp32 mode, RMSNorm folded into the GEMMs: Wqkv diag(ln1), Wgu diag(ln2), group-split
     void *Wqkvf_x = nullptr, *Wo_x = nullptr, *Wguf_x = nullptr, *Wd_x = nullptr;   // MX pipeline: the same four as GX rows + their fp8 exponents
     int ws_qkvf = 0, ws_o = 0, ws_guf = 0, ws_d = 0;
+    void *Wqkv_x = nullptr, *Wgu_x = nullptr;                                 // ModernBERT's MX pipeline (no norm fold): Wqkv and Wi as GX rows (Wo_x, Wd_x above)
+    int ws_qkv = 0, ws_gu = 0;
     float* bqkv_p = nullptr;            // bqkv in the row order of a Wqkvf_x built for the RoPE epilogue (glc_rope_perm128), else null
     bool qkv_perm = false;              // Wqkvf_x's rows are in that order (with or without a bias to go with them)
     float *qn = nullptr, *kn = nullptr; // qk_norm (Qwen3): the gains [head_dim] of self_attn.q_norm / k_norm, f32; else null
@@ -71,6 +73,8 @@ struct glc_engine {
     bool dec_split = false;         // decoder backbone, fp32 mode: RoPE/layout pass writes split-f16 units, grouped-query attention on three-MFMA products
     bool attn_split = false;        // fp32 mode: band attention on split-f16 operands (three f16 MFMAs per product); GLICLASS_F32_ATTN=native turns it off
     bool mx_built = false, mx = false;   // MX cross-term projections (gemm256x.hip) on GX rows: allowed for this engine / pipeline selected (GLICLASS_MX, glc_debug_set_mx)
+    int mx_env = 0;                      // GLICLASS_MX at creation: 0 unset / other, 1 "0", 2 "build" (glc_engine_enable_mx reads it on the ModernBERT backbone)
+    float mb_ln_bound = 0.f;             // ModernBERT: max |gamma| sqrt(H) over the norms whose rows become GX operands (the activation exponent glc_engine_enable_mx picks)
     bool mx_ready = false;               // ... and the GX copies of the projection weights exist: built from the split-f16 copies by the first forward that takes the pipeline
     size_t mx_bytes = 0;                 // their size (glc_debug_mx_weight_bytes)
     bool last_mx = false;                // the last forward ran the MX pipeline

@@ -74,8 +74,11 @@ __device__ __forceinline__ void x_tile_of_block(const GemmArgs& p, int ntn, int&
 // 32x32x64 with the NEXT group's f16 fragment reads and its 16 DMA pieces of the group after that between them — every fragment register is loaded one phase
 // (1024 matrix-pipe cycles) before its use and dies with its phase, so no fragment is double-buffered (a16 / w16 / xa / xw: 128 registers), ONE barrier per group.
 // LDS reads per group and CU 128 KiB instead of 192; requests enter the vector-memory path one per MFMA gap instead of in bursts.
-template <int EPI, bool VMODE, bool W128 = false>
+// EPI_RESIDP = EPI_RESID with the residual rows as plain fp32 (RPLAIN; its own build, so that the GX-residual build keeps its registers)
+template <int EPI_IN, bool VMODE, bool W128 = false>
 __device__ __forceinline__ void gemm256x_tile(const GemmArgs& p, int n_tile0, int ntn) {
+    constexpr bool RPLAIN = EPI_IN == EPI_RESIDP;
+    constexpr int EPI = RPLAIN ? (int)EPI_RESID : EPI_IN;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm_outer = W128 ? (wave >> 1) : (wave >> 2), wn_outer = W128 ? (wave & 1) : (wave & 3);
     const int c32 = lane & 31, h = lane >> 5;
@@ -309,13 +312,14 @@ __device__ __forceinline__ void gemm256x_tile(const GemmArgs& p, int n_tile0, in
     const int qkv_b0 = (EPI == EPI_QKV || EPI == EPI_QKVR) ? m0 / p.Sp : 0;
     const float kHi = gx_act_khi(p.act_sc), kLo = gx_act_klo(p.act_sc), kInvLo = gx_pow2_inv(kLo);       // activation rows in and out: exponent act_sc
     constexpr float kInvLo0 = 1.0f / (float)(1 << GLC_GX_SHIFT);                                          // MX tiles (attention operands): exponent 0       // activation rows: exponent 0
-    if constexpr (EPI == EPI_SWIGLU) {
+    if constexpr (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) {
         // W rows alternate 16 gate / 16 up features (engine.hip interleaves them at load): in D[n = 32 J + 8 q + 4 h + e][m] the register quads
         // q = 0, 1 hold gate features 8 q + 4 h + e of block J and q + 2 the matching up features — same lane, no exchange.  The wave's
         // 128 x 64 sub-tile becomes 128 x 32 outputs silu(gate) * up (Q2:47); patch [32 rows][32 features], row stride 36 floats.
         // RMSNorm folded into this GEMM (a_stats: W holds W diag(gain), the rows are raw): gate and up scale by the row's rstd first.
+        // EPI_GEGLU (ModernBERT, MB:89-91): the same quads hold [input | gate], the output is gelu(input) * gate with the erf GELU of EPI_GELU; no folded norm.
         const int Iw = N >> 1;
-        const bool lnf = p.a_stats != nullptr;
+        const bool lnf = EPI == EPI_SWIGLU && p.a_stats != nullptr;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float rs = lnf ? p.a_stats[m0 + wm * 128 + c * 32 + c32].y : 1.0f;
@@ -325,10 +329,15 @@ __device__ __forceinline__ void gemm256x_tile(const GemmArgs& p, int n_tile0, in
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     f32x4 v;
+                    if constexpr (EPI == EPI_GEGLU) {
+                        const f32x2 g0 = glc_gelu2_f32((f32x2){acc[c][J][4 * q], acc[c][J][4 * q + 1]}), g1 = glc_gelu2_f32((f32x2){acc[c][J][4 * q + 2], acc[c][J][4 * q + 3]});
+                        v = (f32x4){g0[0] * acc[c][J][4 * (q + 2)], g0[1] * acc[c][J][4 * (q + 2) + 1], g1[0] * acc[c][J][4 * (q + 2) + 2], g1[1] * acc[c][J][4 * (q + 2) + 3]};
+                    } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float gt = acc[c][J][4 * q + e] * rs, up = acc[c][J][4 * (q + 2) + e] * rs;
                         v[e] = gt * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * gt)) * up;
+                    }
                     }
                     *reinterpret_cast<f32x4*>(stg + c32 * 36 + 16 * J + 8 * q + 4 * h) = v;
                 }
@@ -372,26 +381,37 @@ __device__ __forceinline__ void gemm256x_tile(const GemmArgs& p, int n_tile0, in
         }
         // residual rows (GX) one 32-row chunk ahead of their use: lane = 8 consecutive columns
         gs_h8 rpre[4]; u32x2 rpre_lo[4]; float2 rst_pre[4];
-        auto load_resid = [&](int c, gs_h8 (&r)[4], u32x2 (&rl)[4], float2 (&rst)[4]) {
+        // (RPLAIN: the 8 fp32 values of a plain residual row instead, ONE buffer loaded at the top of its chunk — behind the patch writes —
+        //  since a second one does not fit the registers)
+        f32x4 pnone[RPLAIN ? 4 : 1][2];
+        auto load_resid = [&](int c, gs_h8 (&r)[4], u32x2 (&rl)[4], float2 (&rst)[4], f32x4 (&pp)[RPLAIN ? 4 : 1][2]) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int idx = lane + 64 * k, row = idx >> 3, g8 = idx & 7;
                 if (rln) rst[k] = p.r_stats[m0 + wm * 128 + c * 32 + row];
                 const int n = n0 + wn * 64 + g8 * 8;
+                if constexpr (RPLAIN) {
+                    const float* fp = reinterpret_cast<const float*>(p.resid) + (size_t)(m0 + wm * 128 + c * 32 + row) * N + n;
+                    pp[k][0] = *reinterpret_cast<const f32x4*>(fp);
+                    pp[k][1] = *reinterpret_cast<const f32x4*>(fp + 4);
+                    continue;
+                }
                 const unsigned char* rp = reinterpret_cast<const unsigned char*>(p.resid) + (size_t)(m0 + wm * 128 + c * 32 + row) * 4 * N + (n >> 5) * 128;
                 r[k] = *reinterpret_cast<const gs_h8*>(rp + (n & 31) * 2);
                 rl[k] = *reinterpret_cast<const u32x2*>(rp + 64 + (n & 31) * 2);
             }
         };
-        if constexpr (EPI == EPI_RESID) { load_resid(0, rpre, rpre_lo, rst_pre); }
+        if constexpr (EPI == EPI_RESID && !RPLAIN) { load_resid(0, rpre, rpre_lo, rst_pre, pnone); }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             gs_h8 rcur[4]; u32x2 rcur_lo[4]; float2 rst_cur[4];
+            f32x4 pcur[RPLAIN ? 4 : 1][2];
             
             if (EPI == EPI_RESID) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { rcur[k] = rpre[k]; rcur_lo[k] = rpre_lo[k]; rst_cur[k] = rst_pre[k]; }
-                if (c + 1 < 4) load_resid(c + 1, rpre, rpre_lo, rst_pre);
+                if constexpr (RPLAIN) load_resid(c, rcur, rcur_lo, rst_cur, pcur);
+                else if (c + 1 < 4) load_resid(c + 1, rpre, rpre_lo, rst_pre, pnone);
             }
             const float2 sm = lnf ? p.a_stats[m0 + wm * 128 + c * 32 + c32] : make_float2(0.f, 1.f);
             
@@ -460,6 +480,10 @@ __device__ __forceinline__ void gemm256x_tile(const GemmArgs& p, int n_tile0, in
                 const int n = n0 + wn * 64 + g8 * 8;
                 if constexpr (EPI == EPI_RESID) {
                     float r[8];
+                    if constexpr (RPLAIN) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { r[e] = pcur[k][0][e]; r[4 + e] = pcur[k][1][e]; }
+                    } else
                     gx_decode8(rcur[k], rcur_lo[k], kInvLo, r);
                     if (rln) {           // raw residual row: LayerNorm on the fly
                         const float2 rs = rst_cur[k];
@@ -724,6 +748,7 @@ bool glc_gemm256x_supported(const GemmArgs& a, int epi) {
     if (epi == EPI_QKV) return a.H % 256 == 0 && a.N == 3 * a.H && a.Sp % 64 == 0 && a.Sp >= 64 && a.nh * 64 == a.H;
     if (epi == EPI_QKVR) return a.nq > 0 && a.nkv > 0 && a.nq % 2 == 0 && a.nkv % 2 == 0 && a.N == (a.nq + 2 * a.nkv) * 128 && a.Sp % 32 == 0 && a.Sp >= 32 &&
                                 a.Mvalid > 0 && a.Mvalid % a.Sp == 0 && a.Mvalid <= a.Mpad;
+    if (epi == EPI_GEGLU) return a.glu_interleaved != 0;          // (the caller vouches for the row order of W: glc_kernels.h)
     return epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESID || epi == EPI_SWIGLU;
 }
 
@@ -742,8 +767,13 @@ const char* glc_launch_gemm256x(hipStream_t st, int epi, const GemmArgs& a_in) {
     switch (epi) {
         case EPI_BIAS: return launch_x<EPI_BIAS, false>(st, a, 0, ntn);
         case EPI_GELU: return launch_x<EPI_GELU, false>(st, a, 0, ntn);
-        case EPI_RESID: return launch_x<EPI_RESID, false>(st, a, 0, ntn);
+        case EPI_RESID:
+            if (!a.gs_resid_plain) return launch_x<EPI_RESID, false>(st, a, 0, ntn);
+            // plain fp32 residual rows (ModernBERT's MX pipeline: the residual stream itself): the 8-wave tile's own build, plain fp32 out
+            return a.ln_part || a.r_stats ? "gemm256x: a plain fp32 residual takes no statistics and writes plain fp32 rows" : launch_x<EPI_RESIDP, false>(st, a, 0, ntn);
         case EPI_SWIGLU: return a.bias ? "gemm256x: the SwiGLU epilogue takes no bias" : launch_x<EPI_SWIGLU, false>(st, a, 0, ntn);
+        // (the 8-wave tile only: the one-wave tile has no GeGLU build)
+        case EPI_GEGLU: return a.bias || a.a_stats ? "gemm256x: the GeGLU epilogue takes no bias and no folded norm" : launch_x<EPI_GEGLU, false>(st, a, 0, ntn);
         case EPI_QKV: {
             const int nqk = 2 * a.H / TN, nq = a.qkv_skip_q ? a.H / TN : 0;
             const char* m = launch_x<EPI_QKV, false>(st, a, nq, nqk - nq);      // (one launch for both, as EPI_QKVR below: measured +-0 at c3 — 6 + 3 full rounds either way)

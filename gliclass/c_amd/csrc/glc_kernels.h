@@ -9,7 +9,8 @@ enum { GLC_DT_F32 = 0, GLC_DT_BF16 = 1, GLC_DT_F16 = 2 };  // == GLC_F32/BF16/F1
 enum { EPI_BIAS = 0, EPI_GELU = 1, EPI_RESID = 2, EPI_QKV = 3,
        EPI_SWIGLU = 4,     // gemm256s / gemm256x: W rows interleave 16 gate / 16 up features; C [Mpad, N/2] = silu(gate) * up
        EPI_QKVR = 5,       // gemm256x only, decoder backbone: RoPE + softmax scale + the MX tiles of decoder_mx.hip written by the epilogue (rope_cs ..)
-       EPI_GEGLU = 6 };    // gemm256s only, ModernBERT: W rows interleave 16 input / 16 gate features; C [Mpad, N/2] = gelu(input) * gate
+       EPI_GEGLU = 6,    // gemm256s / gemm256x (8-wave tile, with GemmArgs::glu_interleaved), ModernBERT: W rows interleave 16 input / 16 gate features; C [Mpad, N/2] = gelu(input) * gate
+       EPI_RESIDP = 7 };   // gemm256x's own build of EPI_RESID with gs_resid_plain (plain fp32 residual rows); callers pass EPI_RESID
 
 // Developer A/B switches (GLC_* environment variables: kernel variants kept for same-box comparisons, docs/LOG_r01-r05.md §7) are read only by a
 // library built with -DGLC_DEVELOPER (make DEV=1); the product library reads the documented GLICLASS_* knobs and nothing else.
@@ -50,7 +51,8 @@ struct GemmArgs {
     // ws[z][Mpad][N]; a second pass sums the parts in a fixed order and applies the epilogue.  ws_bytes = capacity of ws.
     float* ws = nullptr; size_t ws_bytes = 0;
     // gemm256s on group-split operands (glc_launch_gemm256s_gs): EPI_BIAS / EPI_GELU write C as plain fp32 rows instead of GS rows;
-    // EPI_RESID reads its residual as plain fp32 rows instead of GS rows (decoder backbone: the residual stream itself)
+    // EPI_RESID reads its residual as plain fp32 rows instead of GS rows (decoder backbone: the residual stream itself; gemm256x: instead of
+    // GX rows, with plain fp32 output only — ModernBERT's MX pipeline)
     int gs_c_plain = 0, gs_resid_plain = 0;
     int n_group = 0;                        // gemm256s, set by its launcher: tile order sweeps the M-tiles once per group of n_group N-tiles (0: row-major)
     // QKV (gemm256s), pruned last layer: one byte per 32-row tile of the [Mpad] rows; a workgroup of the Q third whose 256 rows hold no
@@ -78,6 +80,9 @@ struct GemmArgs {
     // of every Q / K head in the order glc_rope_perm128 gives (the two members of a rotate-half pair in one wave's accumulators); the
     // epilogue applies RoPE (rope_cs [Sp][64] (cos, sin)) and qscale (Q) in fp32 and writes Qh / Kh / Vt as the MX tiles of decoder_mx.hip.
     const float* rope_cs = nullptr; float qscale = 1.f; int nq = 0, nkv = 0;
+    // gemm256x, EPI_GEGLU: the caller states that W's rows interleave 16 input / 16 gate features (engine.hip interleave_glu_rows) — an order the
+    // launcher cannot see in the bytes; [input rows | gate rows] would give wrong numbers silently.  Without it the launch is refused.
+    int glu_interleaved = 0;
     int perm_cols = 0;                      // gemm256x, EPI_BIAS with gs_c_plain: columns [0, perm_cols) arrive in that order and are stored at their logical place
 };
 // EPI_QKVR: physical row p (0 .. 127) of a Q / K head of the fused projection weight holds logical feature glc_rope_perm128(p): the 32-blocks
@@ -278,7 +283,7 @@ const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, co
 // and stored, the context rows of the others keep what they held; null = every tile
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0,
-                                          int window = 0,    // window > 0 (head_dim 64, not causal, ctx_gs != 2): keys |q - k| <= window only
+                                          int window = 0,    // window > 0 (head_dim 64, not causal): keys |q - k| <= window only
                                           const unsigned char* tile_flag = nullptr);
 
 // MX pipeline (decoder_mx.hip, round 4): the fused fp32 projection -> RoPE + scale + MX tiles (f16 hi units + fp8 steps, 4 bytes per element),
@@ -286,7 +291,8 @@ const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void*
 const char* glc_launch_qkv_layout_mx(hipStream_t st, const void* QKV, const float* cs, void* Qm, void* Km, void* Vm, int B, int Sp, int nq, int nkv, int d, float qscale,
                                      const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
 const char* glc_launch_attention_gqa_mx(hipStream_t st, const void* Qm, const void* Km, const void* Vm, const float* kbias, const int* klen, const int* kfirst, void* CTX,
-                                        int B, int Sp, int nq, int nkv, int d, int causal, const unsigned char* tile_flag = nullptr);
+                                        int B, int Sp, int nq, int nkv, int d, int causal, const unsigned char* tile_flag = nullptr,
+                                        int win = 0);      // win > 0 (head_dim 64, not causal): keys |q - k| <= win only, per-wave kernel; 0: the K / V^T ring kernel
 
 // dtype conversion fp32 -> T (weights upload), n elements
 const char* glc_launch_convert(hipStream_t st, int dtype, const float* src, void* dst, size_t n);

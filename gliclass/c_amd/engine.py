@@ -121,6 +121,12 @@ class Engine:
         if self.L.glc_debug_set_precision_mask(self.h, int(mask)) != 0:
             raise self._err("glc_debug_set_precision_mask")
 
+    def enable_mx(self):
+        """ModernBERT backbone: build the GX weight copies and select the MX pipeline (opt-in there; raises with the condition that
+        failed).  The other backbones take the pipeline by default: a no-op when it is available to the engine."""
+        if self.L.glc_engine_enable_mx(self.h) != 0:
+            raise self._err("glc_engine_enable_mx")
+
     def set_mx(self, on):
         """MX cross-term pipeline on / off (engine created under GLICLASS_MX=1 or =build)"""
         if self.L.glc_debug_set_mx(self.h, int(bool(on))) != 0:

@@ -130,11 +130,25 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
  * second answer, or outliers in Q / K / V: the split-f16 kernels for good, as GLICLASS_MX=0), and the same forward has to be enqueued again.
  * At most two such repeats per engine lifetime.  Consumers queued on the stream BEHIND the forward (an RCCL all-gather, a D2H copy) read
  * whatever the forward wrote: check before trusting them.  Engines created with GLICLASS_MX=0, 16-bit engines and small forwards never
- * take the MX pipeline and never report this. */
+ * take the MX pipeline and never report this.  A ModernBERT engine takes the MX pipeline only after glc_engine_enable_mx (below) and reports the
+ * fp8 range through glc_engine_sync from then on, like the other backbones; without that call it never does. */
 int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_mask, int B, int S, int C,
                               void* d_logits);
 int glc_engine_sync(glc_engine* e);
 int glc_engine_device_forward_valid(glc_engine* e);      /* 1 valid / 0 repeat the forward / -1 error; the stream must be idle (see above) */
+
+/* Opt-in MX pipeline of the ModernBERT backbone (the DeBERTa and decoder backbones take theirs by default).  Builds the GX copies of the four
+ * projection weights of every layer and selects the pipeline: large fp32-mode forwards (the group-split ones) then run their projections on
+ * the MX cross-term GEMM (GeGLU in its epilogue) and their attention on MX tiles (global layers: the K / V^T ring kernel; local layers: the
+ * windowed per-wave kernel).  Returns 0, or -1 with a message in glc_last_error() naming the condition that failed: fp32 dtype; split-f16
+ * weights and attention (no GLICLASS_F32_GEMM / GLICLASS_F32_ATTN = native); no GLICLASS_MX=0; hidden % 256 == 0; (2 inter) % 256 == 0 and
+ * inter % 32 == 0 (modernbert-large, 2 x 2624 = 5248, is not eligible); head_dim 64; not under glc_debug_keep_hidden.  The activation
+ * exponent is chosen here from the LayerNorm gains (max |gamma| sqrt(hidden) > 448: exponent -5 from the start).  Afterwards GLICLASS_MX=build,
+ * glc_debug_set_mx, glc_debug_set_mx_attention, the glc_debug_last_forward_mx* queries and the fp8 range guard behave as on the decoder
+ * backbone.  On the other backbones: 0 if the MX pipeline is available to the engine, else -1; nothing changes.
+ * Environment: GLICLASS_MX_MODERNBERT=1, read once in glc_engine_create, makes this call for a ModernBERT engine (a failure leaves the
+ * engine as it is and is not an error). */
+int glc_engine_enable_mx(glc_engine* e);
 
 /* Exact last-layer pruning (default on; env GLICLASS_PRUNE_LAST=0 disables), on every backbone: the final layer computes attention
  * output, output projection and FFN (DeBERTa: Q as well) only for the rows the head reads — the pooled row of each sequence ([CLS] /
@@ -245,6 +259,7 @@ typedef struct glc_gemm_run {
     int32_t qkv_skip_q, qkv_split, qkv_mxt, gs_c_plain, gs_resid_plain, perm_cols, prec, mx_ws, act_sc, gx_rows;
     int32_t w_presplit;                                /* GLC_GEMM_RUN_128 on an fp32 engine: W (and W2) through glc_launch_presplit, as the engine loads them */
     int32_t w_from_gs;                                 /* GLC_GEMM_RUN_MX: W through glc_launch_presplit + glc_launch_gs_to_gx (the engine's path) instead of glc_launch_to_gx */
+    int32_t glu_interleaved;                           /* GLC_GEMM_RUN_MX, GeGLU: the caller states that W's rows interleave 16 input / 16 gate features (GemmArgs::glu_interleaved); 0: refused */
     int32_t want_ln_part;                              /* pass an ln_part buffer [Mpad][N / 64] (x, y) */
     int32_t fill;                                      /* byte the outputs, ln_part and the guards are prefilled with */
     uint64_t ws_bytes;                                 /* split-K workspace of the 128-tile kernel; 0 = none */
