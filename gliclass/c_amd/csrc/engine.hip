@@ -28,16 +28,32 @@ struct GxScope {
     ~GxScope() { glc_gx_sat_ptr() = nullptr; glc_gx_act_sc() = 0; }
 };
 
+// Captured-graph replay: drop every cached graph and every remembered key (the stream may still be running one of them)
+void graph_clear(glc_engine* e) {
+    if (e->graphs.empty() || e->capturing) return;
+    bool any = false;
+    for (const GraphEntry& g : e->graphs) any = any || g.exec;
+    if (any) { (void)hipSetDevice(e->device); (void)hipStreamSynchronize(e->stream); }
+    for (GraphEntry& g : e->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    e->graphs.clear();
+}
+
 void* dmalloc(glc_engine* e, size_t bytes, bool zero = true) {
     void* p = nullptr;
     if (bytes == 0) bytes = 16;
+    if (e->capturing) { glc_set_err("allocation inside a captured forward"); return nullptr; }      // (graph_forward then runs this forward eagerly)
     if (hipMalloc(&p, bytes) != hipSuccess) { glc_set_err("hipMalloc failed for " + std::to_string(bytes) + " bytes"); return nullptr; }
     if (zero && hipMemsetAsync(p, 0, bytes, e->stream) != hipSuccess) { glc_set_err("hipMemset failed"); return nullptr; }
     e->allocs.push_back(p);
     return p;
 }
 void dfree(glc_engine* e, void* p) {
-    if (!p) return;
+    if (!p || e->capturing) return;        // (capturing: the buffer stays in allocs; the allocation that follows refuses)
+    // A cached graph may hold this address.  Deliberately conservative: EVERY freed engine buffer bumps the generation and drops the cache
+    // (with graphs cached that is a stream synchronise), also one no graph can name — a load-time temporary, the hidden dump.  Frees happen
+    // at load, when the workspace grows and on the first forward of a pipeline, never in steady state, and tracking which buffers a
+    // graph names would buy nothing there.
+    ++e->ws_gen; graph_clear(e);
     for (size_t i = 0; i < e->allocs.size(); ++i)
         if (e->allocs[i] == p) { e->allocs[i] = e->allocs.back(); e->allocs.pop_back(); break; }
     (void)hipFree(p);
@@ -969,6 +985,107 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
     }
 }
 
+// Captured-graph replay (opt-in, glc_engine_set_graph_replay).  A forward of a few rows is a hundred and more launches of a few
+// microseconds each; replay makes their submission one call for a caller that sends the same shapes again and again (measured: no throughput
+// gain with the stream kept full — the device's time per launch bounds such a forward, profiles/graph_replay/summary.txt).  Per key
+// (GraphKey: shape, pipeline switches, workspace generation, the three device pointers): the FIRST forward runs eagerly — it has sized the
+// workspace, built the tables and the MX weights, raised the LDS limits and allocated the gated FFN's rows before it returns —, the SECOND
+// is captured on the engine's one stream (a linear chain: no forks, no events), instantiated and launched, every later one is one
+// hipGraphLaunch.  The captured region is run_forward alone: kernel launches, device-to-device copies and memsets on buffers whose
+// addresses the key pins.  H2D / D2H copies of the host-buffer entry, the range guard's counter read and every host decision stay outside.
+GraphKey graph_key(const glc_engine* e, const void* ids, const void* mask, int B, int S, int C, const void* d_logits) {
+    GraphKey k;
+    k.backbone = e->cfg.backbone; k.B = B; k.S = S; k.Sp = round_up(S, 64); k.C = C;
+    k.gs_mode = e->gs_mode; k.mx = e->mx && e->mx_built ? 1 : 0; k.mx_attn = e->mx_attn ? 1 : 0; k.ln_fused = e->ln_fused ? 1 : 0;
+    k.prune = e->prune_last ? 1 : 0; k.attn_impl = e->attn_impl; k.prec_mask = e->prec_mask; k.act_sc = e->act_sc; k.sticky = e->fp8_sticky_off ? 1 : 0;
+    k.full_lines = glc_gemm_full_lines();
+    k.ws_gen = e->ws_gen; k.ids = ids; k.mask = mask; k.logits = d_logits;
+    return k;
+}
+GraphEntry* graph_find(glc_engine* e, const GraphKey& k) {
+    for (GraphEntry& g : e->graphs) if (g.key == k) return &g;
+    return nullptr;
+}
+int graph_count(const glc_engine* e) {
+    int n = 0;
+    for (const GraphEntry& g : e->graphs) n += g.exec ? 1 : 0;
+    return n;
+}
+// drop the least recently used entry (execs_only: among those that hold an executable)
+void graph_evict(glc_engine* e, bool execs_only) {
+    int lru = -1;
+    for (size_t i = 0; i < e->graphs.size(); ++i)
+        if ((!execs_only || e->graphs[i].exec) && (lru < 0 || e->graphs[i].tick < e->graphs[lru].tick)) lru = (int)i;
+    if (lru < 0) return;
+    if (e->graphs[lru].exec) { (void)hipStreamSynchronize(e->stream); (void)hipGraphExecDestroy(e->graphs[lru].exec); }
+    e->graphs.erase(e->graphs.begin() + lru);
+}
+void graph_note_last(const glc_engine* e, GraphEntry& g) {
+    g.gs = e->last_gs; g.lnf = e->last_lnf; g.mx = e->last_mx; g.mx_attn = e->last_mx_attn; g.rope_epi = e->last_rope_epi; g.pruned = e->last_pruned;
+}
+
+// run_forward, or its captured graph.  Sets e->last_graph.  Caller holds e->mu and has called ensure_capacity.
+bool graph_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
+    e->last_graph = 0;
+    // event bracketing, the hidden-state dump and a stopped forward are not replayed
+    if (!e->graph_on || e->profile || e->keep_hidden || e->debug_stop >= 0) return run_forward(e, ids, mask, B, S, C, d_logits);
+    const GraphKey key = graph_key(e, ids, mask, B, S, C, d_logits);
+    GraphEntry* g = graph_find(e, key);
+    if (g && g->exec) {
+        if (hipGraphLaunch(g->exec, e->stream) == hipSuccess) {
+            g->tick = ++e->graph_tick;
+            e->last_gs = g->gs; e->last_lnf = g->lnf; e->last_mx = g->mx; e->last_mx_attn = g->mx_attn; e->last_rope_epi = g->rope_epi; e->last_pruned = g->pruned;
+            e->lastB = B; e->lastS = S; e->lastSp = key.Sp;
+            e->last_graph = 2;
+            return true;
+        }
+        (void)hipGetLastError();            // (refused: nothing was enqueued — this key runs eagerly from now on)
+        (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; g->ineligible = true;
+        return run_forward(e, ids, mask, B, S, C, d_logits);
+    }
+    if (g && !g->ineligible) {
+        // second forward of the key: capture.  Thread-local mode: a session runs one host thread per engine, and another thread's hipMalloc
+        // must not invalidate this capture.  Whatever goes wrong — a launcher that refuses, an allocation (dmalloc refuses while capturing),
+        // an error from the runtime — ends the capture, destroys what was recorded and runs the forward eagerly: nothing half-captured runs.
+        g->tick = ++e->graph_tick;
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            e->capturing = true;
+            const bool ok = run_forward(e, ids, mask, B, S, C, d_logits);
+            e->capturing = false;
+            const hipError_t ce = hipStreamEndCapture(e->stream, &graph);
+            if (ok && ce == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
+            if (graph) (void)hipGraphDestroy(graph);
+            if (!ok || ce != hipSuccess) exec = nullptr;
+        }
+        if (exec) {
+            if (graph_count(e) >= kGraphCacheMax) { graph_evict(e, true); g = graph_find(e, key); }
+            if (g && hipGraphLaunch(exec, e->stream) == hipSuccess) {
+                g->exec = exec;
+                graph_note_last(e, *g);
+                e->last_graph = 1;
+                return true;
+            }
+            (void)hipGraphExecDestroy(exec);
+        }
+        (void)hipGetLastError();
+        if ((g = graph_find(e, key))) g->ineligible = true;
+        return run_forward(e, ids, mask, B, S, C, d_logits);
+    }
+    if (!run_forward(e, ids, mask, B, S, C, d_logits)) return false;
+    if (!g) {
+        // warmed up: the key as it reads NOW (the forward may have freed a buffer — the gated FFN's rows — or lost the MX pipeline)
+        const GraphKey now = graph_key(e, ids, mask, B, S, C, d_logits);
+        if (!graph_find(e, now)) {
+            if ((int)e->graphs.size() >= kGraphKeysMax) graph_evict(e, false);
+            GraphEntry n; n.key = now; n.tick = ++e->graph_tick;
+            e->graphs.push_back(n);
+        }
+    }
+    return true;
+}
+
 // the largest tensor (in floats) a backbone's loader sends through the staging buffer: the embedding, the fused QKV weight (the folded
 // copy goes up in one piece) or the FFN's input weight (the gated FFNs' [first | second] rows in one piece)
 size_t staging_floats(const glc_model_config& c) {
@@ -1358,6 +1475,10 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
         if (ov && !strcmp(ov, "1") && glc_engine_enable_mx(e) != 0)
             fprintf(stderr, "gliclass: GLICLASS_MX_MODERNBERT=1 has no effect on this engine (%s)\n", glc_last_error());
     }
+    // Captured-graph replay is opt-in as well; the environment makes the call glc_engine_set_graph_replay documents (read once, here)
+    if (const char* gv = getenv("GLICLASS_GRAPH_REPLAY"))
+        if (!strcmp(gv, "1") && glc_engine_set_graph_replay(e, 1) != 0)
+            fprintf(stderr, "gliclass: GLICLASS_GRAPH_REPLAY=1 has no effect on this engine (%s)\n", glc_last_error());
     return e;
 }
 
@@ -1370,6 +1491,7 @@ int glc_engine_enable_mx(glc_engine* e) {
         glc_set_err("enable_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1;
     }
     if (e->mx_built && e->mx_ready) return 0;
+    graph_clear(e);
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, I = c.inter;
     const char* why = nullptr;
@@ -1405,6 +1527,7 @@ void glc_engine_destroy(glc_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    graph_clear(e);
     for (void* p : e->allocs) (void)hipFree(p);
     if (e->h_gxsat) (void)hipHostFree(e->h_gxsat);
     for (auto& v : e->evs) { (void)hipEventDestroy(v.a); (void)hipEventDestroy(v.b); }
@@ -1422,6 +1545,7 @@ static void settle_device_range_check(glc_engine* e) {
     const bool rows = e->h_gxsat[0] != e->gxsat_seen[0], tiles = e->h_gxsat[1] != e->gxsat_seen[1];
     e->gxsat_seen[0] = e->h_gxsat[0]; e->gxsat_seen[1] = e->h_gxsat[1];
     if (!rows && !tiles) return;
+    graph_clear(e);      // (the guard's answer changes the arithmetic of every later forward)
     if (rows && !tiles && e->act_sc == 0) { e->act_sc = kActScLow; e->device_invalid = 1; }
     else { e->fp8_sticky_off = true; e->device_invalid = 2; }
 }
@@ -1456,7 +1580,7 @@ static int forward_one(glc_engine* e, const int64_t* ids, const int64_t* mask, i
     unsigned sat_now[2] = {e->gxsat_seen[0], e->gxsat_seen[1]};
     bool tried_unfused = false, tried_split = false, tried_low = false;
     for (int attempt = 0; attempt < 4; ++attempt) {      // at most: MX, MX with exponent kActScLow, split-f16, norms unfused
-        if (!run_forward(e, e->d_ids, e->d_mask, B, S, c_alloc, e->d_logits)) return -1;
+        if (!graph_forward(e, e->d_ids, e->d_mask, B, S, c_alloc, e->d_logits)) return -1;
         HIPCHK(hipMemcpyAsync(cnt, e->cls_cnt, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, e->stream), -1);
         if (c_alloc > 0) HIPCHK(hipMemcpyAsync(logits, e->d_logits, (size_t)B * c_alloc * sizeof(float), hipMemcpyDeviceToHost, e->stream), -1);
         HIPCHK(hipMemcpyAsync(sat_now, e->d_gxsat, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream), -1);
@@ -1469,6 +1593,7 @@ static int forward_one(glc_engine* e, const int64_t* ids, const int64_t* mask, i
         e->gxsat_seen[0] = sat_now[0]; e->gxsat_seen[1] = sat_now[1];
         if (sat_rows && !sat_tiles && e->last_mx && e->act_sc == 0 && !tried_low) {      // first answer: activation rows with exponent kActScLow, still on the MX pipeline (kept for this engine)
             tried_low = true;
+            graph_clear(e);
             e->act_sc = kActScLow;
             e->fp8_retries++;
             fprintf(stderr, "gliclass: activations beyond the fp8 range of the MX operand images (|x| > 448); this engine's activation rows now carry exponent %d (|x| up to %d)\n", kActScLow, 448 << -kActScLow);
@@ -1476,6 +1601,7 @@ static int forward_one(glc_engine* e, const int64_t* ids, const int64_t* mask, i
         }
         if (sat && e->last_mx && !tried_split) {      // (before the non-finite check: beyond 464 the unclamped e4m3 parts are NaN — glc_common.h gx_split8 — so such a forward may well be non-finite)
             tried_split = true;
+            graph_clear(e);
             e->mx = false;                  // retry: three f16 MFMAs per product, operands up to 65504
             e->fp8_retries++;
             if (++e->fp8_streak >= kFp8Sticky && !e->fp8_sticky_off) {
@@ -1486,6 +1612,7 @@ static int forward_one(glc_engine* e, const int64_t* ids, const int64_t* mask, i
         }
         if (!finite && !tried_unfused && e->dtype == GLC_F32 && e->last_lnf) {
             tried_unfused = true;
+            graph_clear(e);
             e->ln_fused = false;            // retry: norms unfused (this also leaves the MX pipeline)
             e->range_retries++;
             continue;
@@ -1585,6 +1712,12 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
         if (cuts.size() > 2) {
             std::vector<int64_t> gi, gm;
             std::vector<float> gl;
+            int lg = 2;      // glc_debug_last_forward_graph: the minimum over the groups
+            // (graph replay: size the workspace for every group before the first one runs — a buffer that a later group moves would drop the
+            //  graphs and the warmed-up keys of the groups ahead of it)
+            if (e->graph_on)
+                for (size_t g = 0; g + 1 < cuts.size(); ++g)
+                    if (!ensure_capacity(e, cuts[g + 1] - cuts[g], std::max(len[order[cuts[g]]], 1), c_alloc)) return -1;
             for (size_t g = 0; g + 1 < cuts.size(); ++g) {
                 const int i0 = cuts[g], n = cuts[g + 1] - cuts[g];
                 int Sg = len[order[i0]];
@@ -1596,6 +1729,7 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
                 }
                 std::vector<int> gc(n);
                 if (forward_one(e, gi.data(), gm.data(), n, Sg, gl.data(), c_alloc, gc.data()) != 0) return -1;
+                lg = e->last_graph < lg ? e->last_graph : lg;
                 for (int r = 0; r < n; ++r) {
                     cnt[order[i0 + r]] = gc[r];
                     if (c_alloc > 0) memcpy(logits + (size_t)order[i0 + r] * c_alloc, gl.data() + (size_t)r * c_alloc, (size_t)c_alloc * sizeof(float));
@@ -1605,6 +1739,7 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
             for (int b = 0; b < B; ++b) cmax = cnt[b] > cmax ? cnt[b] : cmax;
             if (c_out) *c_out = cmax;
             e->last_groups = (int)cuts.size() - 1;
+            e->last_graph = lg;
             return 0;
         }
     }
@@ -1635,6 +1770,8 @@ long long glc_debug_mx_weight_bytes(const glc_engine* e) { return e ? (long long
 
 int glc_engine_set_length_buckets(glc_engine* e, int max_groups) {
     if (!e || max_groups < 1 || max_groups > 64) { glc_set_err("set_length_buckets: 1..64 groups"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->max_buckets = max_groups;
     return 0;
 }
@@ -1647,7 +1784,7 @@ int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_ma
     if (!ensure_capacity(e, B, S, C)) return -1;
     const bool mx_saved = e->mx;
     if (e->fp8_sticky_off) e->mx = false;
-    const bool ok = run_forward(e, (const int64_t*)d_ids, (const int64_t*)d_mask, B, S, C, (float*)d_logits);
+    const bool ok = graph_forward(e, (const int64_t*)d_ids, (const int64_t*)d_mask, B, S, C, (float*)d_logits);
     e->mx = mx_saved;
     if (!ok) return -1;
     // fp8 range guard (forward_one): a device-resident forward cannot be repeated behind the caller's back — the counter travels to a pinned
@@ -1733,6 +1870,7 @@ float glc_timer_stop_ms(glc_engine* e) {
 int glc_profile_enable(glc_engine* e, int on) {
     if (!e) return -1;
     std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->profile = on != 0;
     e->ev_used = 0;
     for (int i = 0; i < PC_N; ++i) { e->prof_ms[i] = 0.f; e->prof_n[i] = 0; }
@@ -1748,6 +1886,8 @@ int glc_profile_read(glc_engine* e, const char** names, float* total_ms, int* la
 
 int glc_debug_set_group_split(glc_engine* e, int mode) {
     if (!e || mode < 0 || mode > 2) { glc_set_err("group_split: 0 off, 1 auto, 2 whenever the shapes allow"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->gs_mode = mode;
     return 0;
 }
@@ -1757,6 +1897,7 @@ int glc_debug_set_mx(glc_engine* e, int on) {
     if (!e) return -1;
     if (on && !e->mx_built) { glc_set_err("set_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->mx = on != 0;
     if (on) { e->fp8_sticky_off = false; e->fp8_streak = 0; e->act_sc = 0; }      // (a developer switching MX back on also clears the range guard's verdict)
     return 0;
@@ -1765,16 +1906,17 @@ int glc_debug_last_forward_mx(const glc_engine* e) { return e ? (e->last_mx ? 1 
 int glc_debug_last_forward_mx_attention(const glc_engine* e) { return e ? (e->last_mx && e->last_mx_attn ? 1 : 0) : -1; }
 int glc_debug_last_forward_rope_epilogue(const glc_engine* e) { return e ? (e->last_mx && e->last_mx_attn && e->last_rope_epi ? 1 : 0) : -1; }
 /* MX pipeline: attention on MX tiles (1, default) or on split-f16 units (0). */
-int glc_debug_set_mx_attention(glc_engine* e, int on) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); e->mx_attn = on != 0; return 0; }
+int glc_debug_set_mx_attention(glc_engine* e, int on) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); graph_clear(e); e->mx_attn = on != 0; return 0; }
 /* Developer: stop the next forwards after stage 10 * layer + k (k = 0 QKV, 1 attention, 2 attention-output, 3 FFN1, 4 FFN2 + LayerNorm;
  * -1 = run to the end; logits are garbage when stopped); glc_debug_read_workspace (engine_debug.hip) then reads the workspace rows. */
-int glc_debug_set_stop(glc_engine* e, int stage) { if (!e) return -1; e->debug_stop = stage; return 0; }
+int glc_debug_set_stop(glc_engine* e, int stage) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); graph_clear(e); e->debug_stop = stage; return 0; }
 /* Group-split pipeline with LayerNorm folded into the GEMMs (1, default) or as kernels of its own (0).  The folded weights are built
  * at load unless GLC_LNF=0 was set then; without them the switch has no effect. */
 int glc_debug_last_forward_ln_folded(const glc_engine* e) { return e ? (e->last_lnf ? 1 : 0) : -1; }
 int glc_debug_set_ln_fused(glc_engine* e, int on) {
     if (!e) return -1;
     std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->ln_fused = on != 0;
     return 0;
 }
@@ -1782,19 +1924,33 @@ int glc_debug_set_ln_fused(glc_engine* e, int on) {
 int glc_debug_set_precision_mask(glc_engine* e, int mask) {
     if (!e || mask < 0 || mask >= (1 << 15)) { glc_set_err("precision_mask: 15 bits"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->prec_mask = mask;
     return 0;
 }
 /* 256-tile GEMM: full-line ring stages on / off, process-wide (developer A/B switch; results are bit-identical either way). */
 int glc_debug_set_gemm_full_lines(int on) { glc_gemm_set_full_lines(on); return 0; }
-int glc_debug_keep_hidden(glc_engine* e, int on) { if (!e) return -1; e->keep_hidden = on != 0; return 0; }
-int glc_engine_set_prune_last_layer(glc_engine* e, int on) { if (!e) return -1; e->prune_last = on != 0; return 0; }
+int glc_debug_keep_hidden(glc_engine* e, int on) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); graph_clear(e); e->keep_hidden = on != 0; return 0; }
+int glc_engine_set_prune_last_layer(glc_engine* e, int on) { if (!e) return -1; std::lock_guard<std::mutex> lk(e->mu); graph_clear(e); e->prune_last = on != 0; return 0; }
 int glc_debug_last_forward_pruned(const glc_engine* e) { return e ? (e->last_pruned ? 1 : 0) : -1; }
 int glc_debug_set_attention_impl(glc_engine* e, int impl) {
     if (!e || impl < 0 || impl > 3) { glc_set_err("bad attention impl"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
     e->attn_impl = impl;
     return 0;
 }
+
+/* Captured-graph replay of forwards (include/gliclass_hip.h; graph_forward above).  Off drops every cached graph. */
+int glc_engine_set_graph_replay(glc_engine* e, int on) {
+    if (!e) { glc_set_err("set_graph_replay: null engine"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
+    e->graph_on = on != 0;
+    return 0;
+}
+int glc_debug_last_forward_graph(const glc_engine* e) { return e ? e->last_graph : -1; }
+int glc_debug_graph_cache_size(const glc_engine* e) { return e ? graph_count(e) : -1; }
 
 const glc_model_config* glc_engine_config(const glc_engine* e) { return e ? &e->cfg : nullptr; }
 int glc_engine_dtype(const glc_engine* e) { return e ? e->dtype : -1; }

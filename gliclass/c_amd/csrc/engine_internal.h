@@ -64,6 +64,29 @@ struct LayerW {
     int ws_qkv = 0, ws_qkvf = 0, ws_o = 0, ws_1f = 0, ws_2 = 0;
 };
 
+// Captured-graph replay (glc_engine_set_graph_replay): what a cached forward is filed under — everything that decides which kernels a forward
+// launches or what arguments they get — and what it leaves behind for the glc_debug_last_forward_* queries
+struct GraphKey {
+    int backbone, B, S, Sp, C;
+    int gs_mode, mx, mx_attn, ln_fused, prune, attn_impl, prec_mask, act_sc, sticky, full_lines;
+    unsigned long long ws_gen;
+    const void *ids, *mask, *logits;
+    bool operator==(const GraphKey& o) const {
+        return backbone == o.backbone && B == o.B && S == o.S && Sp == o.Sp && C == o.C && gs_mode == o.gs_mode && mx == o.mx && mx_attn == o.mx_attn &&
+               ln_fused == o.ln_fused && prune == o.prune && attn_impl == o.attn_impl && prec_mask == o.prec_mask && act_sc == o.act_sc &&
+               sticky == o.sticky && full_lines == o.full_lines && ws_gen == o.ws_gen && ids == o.ids && mask == o.mask && logits == o.logits;
+    }
+};
+struct GraphEntry {
+    GraphKey key;
+    hipGraphExec_t exec = nullptr;      // null: the key has run eagerly once (workspace sized, tables and MX weights built, LDS limits raised)
+    bool ineligible = false;            // its capture failed: eager from now on
+    unsigned long long tick = 0;        // last use (least recently used goes first)
+    bool gs = false, lnf = false, mx = false, mx_attn = false, rope_epi = false, pruned = false;      // the forward's last_* answers
+};
+constexpr int kGraphCacheMax = 16;      // graph executables per engine
+constexpr int kGraphKeysMax = 64;       // ... and keys remembered in all (warmed-up or ineligible ones included)
+
 struct glc_engine {
     glc_model_config cfg{};
     int dtype = GLC_F32, device = 0, attn_impl = 0;
@@ -135,6 +158,13 @@ struct glc_engine {
     std::map<int, std::pair<int, int>> dsat;   // Sp -> (rsat_pos, rsat_neg)
     // last forward
     int lastB = 0, lastS = 0, lastSp = 0;
+    // captured-graph replay of forwards (opt-in: glc_engine_set_graph_replay / GLICLASS_GRAPH_REPLAY=1; engine.hip graph_forward)
+    bool graph_on = false;
+    bool capturing = false;              // the engine stream is in capture: dmalloc / dfree refuse
+    int last_graph = 0;                  // the last forward: 0 eager, 1 captured and launched, 2 replayed
+    unsigned long long ws_gen = 0;       // workspace generation: every freed engine buffer bumps it (a cached graph holds the old addresses)
+    unsigned long long graph_tick = 0;
+    std::vector<GraphEntry> graphs;
     // debug
     bool keep_hidden = false; void* hidden_dump = nullptr; size_t hidden_cap = 0;
     // timing / profile

@@ -786,6 +786,7 @@ const char* glc_launch_gemm256s(hipStream_t st, int dtype, int epi, const GemmAr
     return dtype == GLC_DT_BF16 ? launch_t<bf16_t>(st, epi, a) : launch_t<f16_t>(st, epi, a);
 }
 
+int glc_gemm_full_lines() { return use_full_lines() ? 1 : 0; }
 void glc_gemm_set_full_lines(int on) { g_full_lines.store(on ? 1 : 0, std::memory_order_relaxed); }
 
 bool glc_gemm_small_m(const GemmArgs& a) {

@@ -100,6 +100,7 @@ const char* glc_launch_rows_to_gs_rms(hipStream_t st, const float* X, void* Y, f
 const char* glc_launch_gemm(hipStream_t st, int dtype, int epi, const GemmArgs& a);       // 128x128 tile, any T
 bool glc_gemm256_supported(int dtype, const GemmArgs& a);                                 // shapes the 256x256 LDS-DMA kernel takes (16-bit T)
 const char* glc_launch_gemm256s(hipStream_t st, int dtype, int epi, const GemmArgs& a);   // 256x256 tile, staggered wave groups (gemm256s.hip)
+int glc_gemm_full_lines();                  // its current value (a cached forward graph is filed under it, engine.hip)
 void glc_gemm_set_full_lines(int on);       // gemm256s.hip: full-line (operand-major) ring stages on / off, process-wide (developer A/B; default on, GLC_GEMM_FL=0)
 bool glc_gemm_small_m(const GemmArgs& a);   // gemm256s.hip: too few 256x256 tiles for this device -> use the 128x128 kernel
 // picks the 256x256 LDS-DMA kernel when the shape allows it, else the 128x128 one

@@ -127,6 +127,20 @@ class Engine:
         if self.L.glc_engine_enable_mx(self.h) != 0:
             raise self._err("glc_engine_enable_mx")
 
+    def set_graph_replay(self, on=True):
+        """captured-graph replay of forwards (opt-in): per shape and pipeline the first forward runs eagerly, the second is captured as a
+        HIP graph, later ones are one launch; bit-identical results.  Off drops every cached graph."""
+        if self.L.glc_engine_set_graph_replay(self.h, int(bool(on))) != 0:
+            raise self._err("glc_engine_set_graph_replay")
+
+    def last_graph(self):
+        """the last forward: 0 ran eagerly, 1 was captured and launched, 2 replayed a cached graph (length-bucketed: the minimum over its groups)"""
+        return int(self.L.glc_debug_last_forward_graph(self.h))
+
+    def graph_cache_size(self):
+        """graph executables the engine holds (at most 16)"""
+        return int(self.L.glc_debug_graph_cache_size(self.h))
+
     def set_mx(self, on):
         """MX cross-term pipeline on / off (engine created under GLICLASS_MX=1 or =build)"""
         if self.L.glc_debug_set_mx(self.h, int(bool(on))) != 0:

@@ -150,6 +150,27 @@ int glc_engine_device_forward_valid(glc_engine* e);      /* 1 valid / 0 repeat t
  * engine as it is and is not an error). */
 int glc_engine_enable_mx(glc_engine* e);
 
+/* Captured-graph replay of forwards (opt-in, default 0): for callers that send the same (B, S, C) shapes again and again.  It takes the
+ * host's submission cost of a forward (a hundred and more launches) down to one call.  MEASURED (profiles/graph_replay/summary.txt): with
+ * forwards enqueued back to back the device's own time per launch bounds a small forward, not the submission, and replay is 0.5-1 % SLOWER
+ * at B = 8.  The host's time per call and the latency of a single awaited forward have not been measured.  Leave it off unless you have
+ * measured your own caller.
+ * Per key — backbone, B, S, padded S, C, every pipeline switch, the workspace generation and the three device pointers (the caller's on
+ * glc_engine_forward_device; the engine's own staging buffers on glc_engine_forward, each group of a length-bucketed forward its own key) —
+ * the first forward runs as always, the second is captured on the engine's stream as a HIP graph (one linear chain) and launched, later ones
+ * are one hipGraphLaunch.  Results are bit-identical: the graph holds the same launches on the same buffers and reads the ids, the mask,
+ * the class-token positions and the range guard's counter from device memory at every replay.  H2D / D2H copies of the host-buffer entry,
+ * the fp8 range guard's read and its repeats stay outside the graph and work as before.  Forwards under glc_profile_enable,
+ * glc_debug_keep_hidden or glc_debug_set_stop, and a key whose capture failed, run eagerly.  Every glc_engine_set_* / glc_debug_set_* call,
+ * glc_engine_enable_mx, glc_profile_enable, glc_debug_keep_hidden, a workspace buffer that moves (a larger shape) and every answer of the range
+ * guards drop all cached graphs; at most 16 are kept per engine (least recently used goes first).  A device-resident caller must keep
+ * d_ids / d_mask / d_logits alive while the engine may replay them: free them only after switching replay off, destroying the engine, or any
+ * of the calls above.  Returns 0; -1 (glc_last_error) for a null engine.  Turning it off drops every cached graph.
+ * Environment: GLICLASS_GRAPH_REPLAY=1, read once in glc_engine_create, makes this call (a failure leaves the engine eager, not an error). */
+int glc_engine_set_graph_replay(glc_engine* e, int on);
+int glc_debug_last_forward_graph(const glc_engine* e);     /* the last forward: 0 ran eagerly (warm-up and ineligible forwards included), 1 was captured and launched, 2 replayed a cached graph (length-bucketed: the minimum over its groups); -1: null engine */
+int glc_debug_graph_cache_size(const glc_engine* e);       /* graph executables the engine holds (0 .. 16); -1: null engine */
+
 /* Exact last-layer pruning (default on; env GLICLASS_PRUNE_LAST=0 disables), on every backbone: the final layer computes attention
  * output, output projection and FFN (DeBERTa: Q as well) only for the rows the head reads — the pooled row of each sequence ([CLS] /
  * position 0, or the last attended token with 'last' pooling) and its class tokens; K and V are still made for every position.  Logits
