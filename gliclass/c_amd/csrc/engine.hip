@@ -493,11 +493,17 @@ bool forward_epilogue(glc_engine* e, const void* rows, bool compact, int B, int 
 }
 
 // The group-split projections of a forward: the 256-tile split-f16 kernel (gemm256s.hip), or on the MX pipeline the cross-term kernel on GX rows
+// (small: glc_engine::mx_small — with it on, a launch of an MX forward that has too few 256-tiles for the device runs the 128 tile, gemm128x.hip;
+//  n128 counts those launches)
 struct GemmGs {
-    hipStream_t st; bool mx; int M;
+    hipStream_t st; bool mx; int M; int small = 0; int* n128 = nullptr;
     const char* operator()(int epi, const GemmArgs& a) const {
         if (!mx) return glc_launch_gemm256s_gs(st, epi, a);
         GemmArgs gx = a; gx.gx_rows = M;          // fp8 range guard: the M rows of this forward, not the slack rows up to Mpad
+        if (small > 0 && glc_gemm_small_m(gx) && glc_gemm128x_supported(gx, epi) && (epi != EPI_RESID || !gx.gs_resid_plain) && !gx.perm_cols) {
+            if (n128) ++*n128;
+            return glc_launch_gemm128x(st, epi, gx);
+        }
         return glc_launch_gemm256x(st, epi, gx);
     }
 };
@@ -613,6 +619,7 @@ bool run_forward_decoder(glc_engine* e, const int64_t* ids, const int64_t* mask,
     if (mx && !build_mx_weights(e)) mx = false;          // (no copies: this and every later forward stay on the split-f16 kernels)
     for (int l = 0; mx && l < L; ++l) mx = e->dlayers[l].Wqkvf_x && e->dlayers[l].Wo_x && e->dlayers[l].Wguf_x && e->dlayers[l].Wd_x;
     e->last_mx = mx;
+    e->last_mx128 = 0;
     const bool mxa = mx && mfma && e->mx_attn;      // round 4: the attention of the MX pipeline on MX tiles too (decoder_mx.hip)
     e->last_mx_attn = mxa;
     e->last_rope_epi = false;
@@ -833,21 +840,26 @@ bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask,
     // (same bytes as fp32), written by their producers, so that every projection runs on the 256-tile LDS-DMA kernel with three
     // f16 MFMAs per product (gemm256s.hip, GS).  Needs the split-f16 weights and attention, the pruned last layer (its compact rows go back to plain
     // fp32 and the small-M kernels) and shapes the 256-tile kernel takes; small forwards stay on the 128-tile split-K kernels.
-    bool gs = false;
+    bool gs = false, via_small = false;
     if (dt == GLC_F32 && e->gs_mode > 0 && e->w_presplit && asplit && impl == 3 && prune && H % 256 == 0 && I % 256 == 0) {
         GemmArgs t; t.Mpad = Mpad; t.N = H; t.K = H;
         gs = e->gs_mode == 2 || !glc_gemm_small_m(t);
+        // opt-in (glc_engine_set_mx_small_forwards): a forward that fails only the fill rule of the 256 tile is still admitted, for the MX pipeline
+        // alone — mode 1: when 128-tiles fill the device by the same rule, mode 2: always
+        if (!gs && e->mx_small > 0 && (e->mx_small == 2 || (long long)(Mpad / 128) * (H / 128) * 2 >= glc_device_cus())) gs = via_small = true;
     }
-    e->last_gs = gs;
     // MX pipeline (round 3): the group-split pipeline with GX rows and the MX cross-term GEMM (gemm256x.hip) for every projection of the
     // full layers — a_hi*w_hi as f16 MFMAs, both cross terms as one block-scaled fp8 MFMA.  Needs the LayerNorm fold on every layer.
     bool mx = gs && e->mx && e->mx_built && e->ln_fused && e->prec_mask == 0 && c.layers >= 2;
     for (int l = 0; mx && l < c.layers; ++l) mx = e->layers[l].W1f && (l == 0 || e->layers[l].Wqkvf);       // (the folded split-f16 copies the GX copies are made from)
     if (mx && !build_mx_weights(e)) mx = false;          // (no copies: this and every later forward stay on the split-f16 kernels)
     for (int l = 0; mx && l < c.layers; ++l) mx = e->layers[l].W1f_x && e->layers[l].Wqkv_x && e->layers[l].Wo_x && e->layers[l].W2_x && (l == 0 || e->layers[l].Wqkvf_x);
+    if (via_small && !mx) gs = false;                    // (admitted for the MX pipeline only: without it the forward runs as it always has)
+    e->last_gs = gs;
     e->last_mx = mx;
     e->last_mx_attn = false;
-    const GemmGs gemm_gs{st, mx, M};
+    e->last_mx128 = 0;
+    const GemmGs gemm_gs{st, mx, M, mx ? e->mx_small : 0, &e->last_mx128};
     // 16-bit modes: the same LayerNorm fold on plain rows of T, when all four projections of a layer run on the staggered 256-tile kernel
     bool fold16 = false;
     if (dt != GLC_F32 && e->ln_fused && prune && !e->keep_hidden && e->attn_impl != 1 && H % 256 == 0 && I % 256 == 0 && e->statsA && e->statsB && e->ln_part) {
@@ -998,7 +1010,7 @@ GraphKey graph_key(const glc_engine* e, const void* ids, const void* mask, int B
     k.backbone = e->cfg.backbone; k.B = B; k.S = S; k.Sp = round_up(S, 64); k.C = C;
     k.gs_mode = e->gs_mode; k.mx = e->mx && e->mx_built ? 1 : 0; k.mx_attn = e->mx_attn ? 1 : 0; k.ln_fused = e->ln_fused ? 1 : 0;
     k.prune = e->prune_last ? 1 : 0; k.attn_impl = e->attn_impl; k.prec_mask = e->prec_mask; k.act_sc = e->act_sc; k.sticky = e->fp8_sticky_off ? 1 : 0;
-    k.full_lines = glc_gemm_full_lines();
+    k.full_lines = glc_gemm_full_lines(); k.mx_small = e->mx_small;
     k.ws_gen = e->ws_gen; k.ids = ids; k.mask = mask; k.logits = d_logits;
     return k;
 }
@@ -1022,6 +1034,7 @@ void graph_evict(glc_engine* e, bool execs_only) {
 }
 void graph_note_last(const glc_engine* e, GraphEntry& g) {
     g.gs = e->last_gs; g.lnf = e->last_lnf; g.mx = e->last_mx; g.mx_attn = e->last_mx_attn; g.rope_epi = e->last_rope_epi; g.pruned = e->last_pruned;
+    g.mx128 = e->last_mx128;
 }
 
 // run_forward, or its captured graph.  Sets e->last_graph.  Caller holds e->mu and has called ensure_capacity.
@@ -1034,7 +1047,7 @@ bool graph_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B
     if (g && g->exec) {
         if (hipGraphLaunch(g->exec, e->stream) == hipSuccess) {
             g->tick = ++e->graph_tick;
-            e->last_gs = g->gs; e->last_lnf = g->lnf; e->last_mx = g->mx; e->last_mx_attn = g->mx_attn; e->last_rope_epi = g->rope_epi; e->last_pruned = g->pruned;
+            e->last_gs = g->gs; e->last_lnf = g->lnf; e->last_mx = g->mx; e->last_mx_attn = g->mx_attn; e->last_rope_epi = g->rope_epi; e->last_pruned = g->pruned; e->last_mx128 = g->mx128;
             e->lastB = B; e->lastS = S; e->lastSp = key.Sp;
             e->last_graph = 2;
             return true;
@@ -1479,6 +1492,10 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (const char* gv = getenv("GLICLASS_GRAPH_REPLAY"))
         if (!strcmp(gv, "1") && glc_engine_set_graph_replay(e, 1) != 0)
             fprintf(stderr, "gliclass: GLICLASS_GRAPH_REPLAY=1 has no effect on this engine (%s)\n", glc_last_error());
+    // ... and so is the MX pipeline for forwards below the 256 tile's fill rule (glc_engine_set_mx_small_forwards)
+    if (const char* sv = getenv("GLICLASS_MX_SMALL"))
+        if ((!strcmp(sv, "1") || !strcmp(sv, "2")) && glc_engine_set_mx_small_forwards(e, atoi(sv)) != 0)
+            fprintf(stderr, "gliclass: GLICLASS_MX_SMALL=%s has no effect on this engine (%s)\n", sv, glc_last_error());
     return e;
 }
 
@@ -1950,6 +1967,22 @@ int glc_engine_set_graph_replay(glc_engine* e, int on) {
     return 0;
 }
 int glc_debug_last_forward_graph(const glc_engine* e) { return e ? e->last_graph : -1; }
+
+/* MX pipeline for forwards below the 256 tile's fill rule, on the 128 tile of gemm128x.hip (include/gliclass_hip.h).  DeBERTa backbone only. */
+int glc_engine_set_mx_small_forwards(glc_engine* e, int mode) {
+    if (!e) { glc_set_err("set_mx_small_forwards: null engine"); return -1; }
+    if (mode < 0 || mode > 2) { glc_set_err("set_mx_small_forwards: 0 off, 1 auto, 2 whenever the shapes allow"); return -1; }
+    if (mode > 0 && e->cfg.backbone != GLC_BACKBONE_DEBERTA) {
+        glc_set_err(std::string("set_mx_small_forwards: the 128 tile has no epilogue of the ") +
+                    (e->cfg.backbone == GLC_BACKBONE_DECODER ? "decoder" : "modernbert") + " backbone (DeBERTa engines only)");
+        return -1;
+    }
+    std::lock_guard<std::mutex> lk(e->mu);
+    graph_clear(e);
+    e->mx_small = mode;
+    return 0;
+}
+int glc_debug_last_forward_mx128(const glc_engine* e) { return e ? e->last_mx128 : -1; }
 int glc_debug_graph_cache_size(const glc_engine* e) { return e ? graph_count(e) : -1; }
 
 const glc_model_config* glc_engine_config(const glc_engine* e) { return e ? &e->cfg : nullptr; }

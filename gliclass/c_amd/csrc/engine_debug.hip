@@ -39,7 +39,7 @@ std::vector<double> stamp_sums(const std::vector<unsigned long long>& hs, size_t
 constexpr size_t RUN_GUARD = 1u << 20;     // bytes of guard before and after every output
 // bytes of output i (C, or Qh / Kh / Vt) the launch may write; 0 = that output does not exist (or the shape is one every launcher refuses)
 size_t gemm_run_out_bytes(const glc_gemm_run& r, int dtype, int i) {
-    const bool wide = r.kernel == GLC_GEMM_RUN_GS || r.kernel == GLC_GEMM_RUN_MX;       // GS / GX rows, split units, MX tiles and plain fp32: 4 bytes per element
+    const bool wide = r.kernel == GLC_GEMM_RUN_GS || r.kernel == GLC_GEMM_RUN_MX || r.kernel == GLC_GEMM_RUN_MX128;       // GS / GX rows, split units, MX tiles and plain fp32: 4 bytes per element
     const size_t es = wide ? 4 : esize(dtype);
     if (r.epi == EPI_QKV || r.epi == EPI_QKVR) {
         if (r.Sp <= 0 || r.Mvalid <= 0) return 0;
@@ -176,14 +176,14 @@ float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iter
 
 /* Kernel-level tests: one launcher call on caller-supplied operands, raw bytes back (include/gliclass_hip.h). */
 int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r) {
-    if (!e || !r || r->kernel < GLC_GEMM_RUN_128 || r->kernel > GLC_GEMM_RUN_AUTO || r->epi < EPI_BIAS || r->epi > EPI_GEGLU || r->Mpad <= 0 || r->N <= 0 || r->K <= 0 ||
+    if (!e || !r || r->kernel < GLC_GEMM_RUN_128 || r->kernel > GLC_GEMM_RUN_MX128 || r->epi < EPI_BIAS || r->epi > EPI_GEGLU || r->Mpad <= 0 || r->N <= 0 || r->K <= 0 ||
         r->Mpad > (1 << 20) || r->N > (1 << 20) || r->K > (1 << 20) || !r->A || !r->W || (r->W2 && r->kernel != GLC_GEMM_RUN_128) || r->ws_bytes > (1ull << 30)) {
         glc_set_err("gemm_run: bad args"); return -1;
     }
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device), -1);
     const int dtype = e->dtype, kern = r->kernel;
-    const bool gs = kern == GLC_GEMM_RUN_GS, mx = kern == GLC_GEMM_RUN_MX;
+    const bool gs = kern == GLC_GEMM_RUN_GS, mx = kern == GLC_GEMM_RUN_MX || kern == GLC_GEMM_RUN_MX128;
     const size_t es = gs || mx ? 4 : esize(dtype);
     auto up32 = [](size_t n) { return (n + 31) / 32 * 32; };      // the group converters take whole 32-groups (a row length they cut wrongly is one the launcher refuses)
     const size_t nA = (size_t)r->Mpad * r->K, nW = (size_t)r->N * r->K, nC = (size_t)r->Mpad * r->N;
@@ -268,6 +268,7 @@ int glc_debug_gemm_run(glc_engine* e, glc_gemm_run* r) {
         case GLC_GEMM_RUN_256S: msg = glc_launch_gemm256s(st, dtype, r->epi, g); break;
         case GLC_GEMM_RUN_GS: msg = glc_launch_gemm256s_gs(st, r->epi, g); break;
         case GLC_GEMM_RUN_MX: msg = glc_launch_gemm256x(st, r->epi, g); break;
+        case GLC_GEMM_RUN_MX128: msg = glc_launch_gemm128x(st, r->epi, g); break;
         default: msg = glc_launch_gemm_auto(st, dtype, r->epi, g); break;
     }
     if (msg) return fail(msg, -2);

@@ -68,13 +68,13 @@ struct LayerW {
 // launches or what arguments they get — and what it leaves behind for the glc_debug_last_forward_* queries
 struct GraphKey {
     int backbone, B, S, Sp, C;
-    int gs_mode, mx, mx_attn, ln_fused, prune, attn_impl, prec_mask, act_sc, sticky, full_lines;
+    int gs_mode, mx, mx_attn, ln_fused, prune, attn_impl, prec_mask, act_sc, sticky, full_lines, mx_small;
     unsigned long long ws_gen;
     const void *ids, *mask, *logits;
     bool operator==(const GraphKey& o) const {
         return backbone == o.backbone && B == o.B && S == o.S && Sp == o.Sp && C == o.C && gs_mode == o.gs_mode && mx == o.mx && mx_attn == o.mx_attn &&
                ln_fused == o.ln_fused && prune == o.prune && attn_impl == o.attn_impl && prec_mask == o.prec_mask && act_sc == o.act_sc &&
-               sticky == o.sticky && full_lines == o.full_lines && ws_gen == o.ws_gen && ids == o.ids && mask == o.mask && logits == o.logits;
+               sticky == o.sticky && full_lines == o.full_lines && mx_small == o.mx_small && ws_gen == o.ws_gen && ids == o.ids && mask == o.mask && logits == o.logits;
     }
 };
 struct GraphEntry {
@@ -83,6 +83,7 @@ struct GraphEntry {
     bool ineligible = false;            // its capture failed: eager from now on
     unsigned long long tick = 0;        // last use (least recently used goes first)
     bool gs = false, lnf = false, mx = false, mx_attn = false, rope_epi = false, pruned = false;      // the forward's last_* answers
+    int mx128 = 0;
 };
 constexpr int kGraphCacheMax = 16;      // graph executables per engine
 constexpr int kGraphKeysMax = 64;       // ... and keys remembered in all (warmed-up or ineligible ones included)
@@ -102,6 +103,10 @@ struct glc_engine {
     size_t mx_bytes = 0;                 // their size (glc_debug_mx_weight_bytes)
     bool last_mx = false;                // the last forward ran the MX pipeline
     bool last_mx_attn = false;           // ... and its attention ran on MX tiles (attention_mx.hip)
+    // MX pipeline for forwards below the 256 tile's fill rule (glc_engine_set_mx_small_forwards / GLICLASS_MX_SMALL; DeBERTa backbone): 0 off,
+    // 1 auto (the 128 tile's own fill rule), 2 whenever the shapes allow (tests); their small-M launches run gemm128x.hip
+    int mx_small = 0;
+    int last_mx128 = 0;                  // GEMM launches of the last forward on the 128 tile
     bool last_rope_epi = false;          // ... and (decoder) its QKV projections ran RoPE + MX tiles as their epilogue (gemm256x EPI_QKVR)
     bool dec_rope_epi = true;            // decoder MX pipeline: RoPE + MX tiles as the QKV projection's epilogue (gemm256x EPI_QKVR); GLC_DEC_ROPE_EPI=0: the separate pass
     bool mx_attn = true;                 // MX pipeline: attention on MX tiles (attention_mx.hip); false: split-f16 units (GLC_MX_ATTN=0, glc_debug_set_mx_attention)

@@ -134,6 +134,11 @@ bool glc_gemm256s_gs_supported(const GemmArgs& a, int epi);
 // EPI_RESID: resid as GX rows, C raw GX rows + ln_part, or plain fp32; EPI_QKV: split-f16 units; LayerNorm fold arguments as gemm256s.
 bool glc_gemm256x_supported(const GemmArgs& a, int epi);
 const char* glc_launch_gemm256x(hipStream_t st, int epi, const GemmArgs& a);
+// ... and its 128x128 tile (gemm128x.hip) for forwards with too few 256-tiles to fill the device: the same operands, arithmetic order and epilogue
+// semantics (bit-identical outputs on the same operand images); EPI_BIAS / EPI_GELU / EPI_RESID (GX residual) / EPI_QKV only.  Mpad % 128 == 0,
+// N % 128 == 0, K % 32 == 0; EPI_QKV: H % 128 == 0.  Refusals begin "gemm128x:".
+bool glc_gemm128x_supported(const GemmArgs& a, int epi);
+const char* glc_launch_gemm128x(hipStream_t st, int epi, const GemmArgs& a);
 const char* glc_launch_to_gx(hipStream_t st, void* w, size_t n, int sc, int worder);       // in place: n fp32 values -> GX rows, fp8 exponent sc; worder: weight rows
 // the MX weight copies from the split-f16 (group-split) copies already on the device: largest magnitude (float bits, atomicMax into *d_bits), then the conversion
 const char* glc_launch_gs_absmax(hipStream_t st, const void* gs, size_t n, unsigned* d_bits);

@@ -141,6 +141,17 @@ class Engine:
         """graph executables the engine holds (at most 16)"""
         return int(self.L.glc_debug_graph_cache_size(self.h))
 
+    def set_mx_small_forwards(self, mode):
+        """DeBERTa backbone, fp32 mode (opt-in): MX pipeline for forwards below the 256 tile's fill rule, their small launches on the 128 tile of
+        the MX GEMM.  0 = off, 1 = auto (the 128 tile's own fill rule), 2 = whenever the shapes allow.  Taken forwards move from ~1e-5 to the MX
+        arithmetic's ~4e-5 against the oracle.  Raises on the other backbones for modes >= 1."""
+        if self.L.glc_engine_set_mx_small_forwards(self.h, int(mode)) != 0:
+            raise self._err("glc_engine_set_mx_small_forwards")
+
+    def last_mx128(self):
+        """GEMM launches of the last forward that ran on the 128 tile of the MX GEMM (0: none)"""
+        return int(self.L.glc_debug_last_forward_mx128(self.h))
+
     def set_mx(self, on):
         """MX cross-term pipeline on / off (engine created under GLICLASS_MX=1 or =build)"""
         if self.L.glc_debug_set_mx(self.h, int(bool(on))) != 0:

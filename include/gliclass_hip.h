@@ -171,6 +171,25 @@ int glc_engine_set_graph_replay(glc_engine* e, int on);
 int glc_debug_last_forward_graph(const glc_engine* e);     /* the last forward: 0 ran eagerly (warm-up and ineligible forwards included), 1 was captured and launched, 2 replayed a cached graph (length-bucketed: the minimum over its groups); -1: null engine */
 int glc_debug_graph_cache_size(const glc_engine* e);       /* graph executables the engine holds (0 .. 16); -1: null engine */
 
+/* MX pipeline for mid-size forwards (opt-in, default 0; DeBERTa backbone, fp32 mode).  Which arithmetic an fp32-mode forward gets is decided by
+ * one fill rule, (Mpad / 256) (H / 256) 2 >= CUs: at or above it the group-split / MX pipeline (two matrix-pipe units per product), below it
+ * the 128-tile split-K kernels on split-f16 operands (three units).  With mode >= 1 a forward that fails ONLY that rule is still admitted to
+ * the group-split + MX pipeline, and its GEMM launches with too few 256-tiles for the device run the 128 x 128 tile of the MX GEMM
+ * (csrc/gemm128x.hip: same operands, same arithmetic order, outputs bit-identical to the 256 tile's).  Every other condition of the pipeline
+ * stays: pruned last layer, split-f16 weights and attention, hidden % 256 == 0, inter % 256 == 0, folded LayerNorm, layers >= 2, no
+ * precision mask, MX weight copies buildable.
+ *   mode 0  off: every decision exactly as without this call
+ *   mode 1  auto: admitted when the same fill rule holds for the 128 tile, (Mpad / 128) (H / 128) 2 >= CUs (256 CUs, H = 768: from ~2.8 k rows)
+ *   mode 2  whenever the shapes allow (tests)
+ * PRECISION: a forward taken by the switch moves from the split-f16 arithmetic (~1e-5 per-label probability error against the oracle) to the MX
+ * arithmetic's ~4e-5 — the error large forwards have by default; that is why it is opt-in.  The fp8 range guard, its retries and
+ * glc_engine_sync's report apply unchanged.  Speed: not measured yet; nothing is promised.
+ * Changing the mode drops every cached graph.  Returns 0; -1 (glc_last_error) for a null engine, a mode outside 0 .. 2, or mode >= 1 on the
+ * decoder / ModernBERT backbones (the message names the backbone; mode 0 returns 0 there).
+ * Environment: GLICLASS_MX_SMALL=1|2, read once in glc_engine_create, makes this call (a failure leaves the engine as it is, not an error). */
+int glc_engine_set_mx_small_forwards(glc_engine* e, int mode);
+int glc_debug_last_forward_mx128(const glc_engine* e);     /* GEMM launches of the last forward that ran on the 128 tile (0: none); -1: null engine */
+
 /* Exact last-layer pruning (default on; env GLICLASS_PRUNE_LAST=0 disables), on every backbone: the final layer computes attention
  * output, output projection and FFN (DeBERTa: Q as well) only for the rows the head reads — the pooled row of each sequence ([CLS] /
  * position 0, or the last attended token with 'last' pooling) and its class tokens; K and V are still made for every position.  Logits
@@ -267,7 +286,8 @@ enum { GLC_GEMM_RUN_128 = 0,     /* gemm.hip, the engine's dtype (fp32 engines: 
        GLC_GEMM_RUN_256S = 1,    /* gemm256s.hip, 16-bit engines */
        GLC_GEMM_RUN_GS = 2,      /* gemm256s.hip on group-split rows */
        GLC_GEMM_RUN_MX = 3,      /* gemm256x.hip on GX rows */
-       GLC_GEMM_RUN_AUTO = 4 };  /* glc_launch_gemm_auto, the engine's dtype */
+       GLC_GEMM_RUN_AUTO = 4,    /* glc_launch_gemm_auto, the engine's dtype */
+       GLC_GEMM_RUN_MX128 = 5 }; /* gemm128x.hip on GX rows: operands encoded as for GLC_GEMM_RUN_MX */
 typedef struct glc_gemm_run {
     /* ---- in ---- */
     int32_t kernel, epi;                               /* GLC_GEMM_RUN_*; EPI_* of csrc/glc_kernels.h (0 bias, 1 GELU, 2 residual, 3 QKV, 4 SwiGLU, 5 QKVR, 6 GeGLU) */
