@@ -500,7 +500,7 @@ struct GemmGs {
     const char* operator()(int epi, const GemmArgs& a) const {
         if (!mx) return glc_launch_gemm256s_gs(st, epi, a);
         GemmArgs gx = a; gx.gx_rows = M;          // fp8 range guard: the M rows of this forward, not the slack rows up to Mpad
-        if (small > 0 && glc_gemm_small_m(gx) && glc_gemm128x_supported(gx, epi) && (epi != EPI_RESID || !gx.gs_resid_plain) && !gx.perm_cols) {
+        if (small > 0 && glc_gemm_small_m(gx) && glc_gemm128x_supported(gx, epi)) {
             if (n128) ++*n128;
             return glc_launch_gemm128x(st, epi, gx);
         }

@@ -135,10 +135,26 @@ bool glc_gemm256s_gs_supported(const GemmArgs& a, int epi);
 bool glc_gemm256x_supported(const GemmArgs& a, int epi);
 const char* glc_launch_gemm256x(hipStream_t st, int epi, const GemmArgs& a);
 // ... and its 128x128 tile (gemm128x.hip) for forwards with too few 256-tiles to fill the device: the same operands, arithmetic order and epilogue
-// semantics (bit-identical outputs on the same operand images); EPI_BIAS / EPI_GELU / EPI_RESID (GX residual) / EPI_QKV only.  Mpad % 128 == 0,
-// N % 128 == 0, K % 32 == 0; EPI_QKV: H % 128 == 0.  Refusals begin "gemm128x:".
+// semantics (bit-identical outputs on the same operand images); EPI_BIAS (no perm_cols) / EPI_GELU / EPI_RESID (GX residual) / EPI_QKV only.
+// Mpad % 128 == 0, N % 128 == 0, K % 32 == 0; EPI_QKV: H % 128 == 0.  Refusals begin "gemm128x:".
 bool glc_gemm128x_supported(const GemmArgs& a, int epi);
 const char* glc_launch_gemm128x(hipStream_t st, int epi, const GemmArgs& a);
+// The head of both launchers: the refusals they share and the defaults of the range guard.  Returns the refusal, in the words of the 256 tile's
+// launcher or (tile128) of the 128 tile's, or null: a is then ready to launch.
+inline const char* glc_mx_gemm_prepare(GemmArgs& a, int epi, bool tile128) {
+    if (a.stamps || a.prio_mode >= 4) return tile128 ? "gemm128x: the MX GEMM has no stamped or timing-only build" : "gemm256x: the MX GEMM has no stamped or timing-only build";
+    if (!a.gx_sat) a.gx_sat = glc_gx_sat_ptr();              // fp8 range guard of the activation images this launch writes
+    if (!a.act_sc) a.act_sc = glc_gx_act_sc();               // ... and the exponent of the activation rows (engine.hip act_sc)
+    if (a.gx_rows <= 0) a.gx_rows = a.Mvalid > 0 ? a.Mvalid : a.Mpad;     // ... over the rows that exist (slack rows up to Mpad hold leftovers)
+    if (!(tile128 ? glc_gemm128x_supported(a, epi) : glc_gemm256x_supported(a, epi))) return tile128 ? "gemm128x: unsupported shape" : "gemm256x: unsupported shape";
+    if (!a.A || !a.W) return tile128 ? "gemm128x: null operand" : "gemm256x: null operand";
+    if (epi == EPI_QKV || epi == EPI_QKVR) {
+        if (!a.Qh || !a.Kh || !a.Vt) return tile128 ? "gemm128x: null QKV output" : "gemm256x: null QKV output";
+        if (epi == EPI_QKVR && !a.rope_cs) return "gemm256x: null RoPE table";          // (the 256 tile only: glc_gemm128x_supported)
+    } else if (!a.C) return tile128 ? "gemm128x: null output" : "gemm256x: null output";
+    if (epi == EPI_RESID && !a.resid) return tile128 ? "gemm128x: null residual" : "gemm256x: null residual";
+    return nullptr;
+}
 const char* glc_launch_to_gx(hipStream_t st, void* w, size_t n, int sc, int worder);       // in place: n fp32 values -> GX rows, fp8 exponent sc; worder: weight rows
 // the MX weight copies from the split-f16 (group-split) copies already on the device: largest magnitude (float bits, atomicMax into *d_bits), then the conversion
 const char* glc_launch_gs_absmax(hipStream_t st, const void* gs, size_t n, unsigned* d_bits);
