@@ -15,7 +15,7 @@ SCORER_WEIGHTED_DOT = 1
 SCORER_MLP = 2
 SCORER_MLP_HIDDEN = 256
 SCORER_NAMES = {"simple": SCORER_DOT, "weighted-dot": SCORER_WEIGHTED_DOT, "mlp": SCORER_MLP}
-BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT = 0, 1, 2
+BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT = 0, 1, 2, 3
 
 
 @dataclass(frozen=True)
@@ -56,6 +56,12 @@ class GLiClassConfig:
     # epsilon ln_eps); attn_bias = 0 drops the q / k / v projection biases (Llama, Qwen3).  Qwen2 is (0, 1).
     qk_norm: int = 0
     attn_bias: int = 1
+    # BERT backbone (transformers models/bert, models/roberta, models/xlm_roberta): rows of the learned position table and of the token-type
+    # table (row 0 is the only one used); pos_offset = 0 numbers positions 0 .. S-1 (BERT), pos_offset = pad_id + 1 numbers the non-pad
+    # tokens from pos_offset on and gives pad tokens row pad_id (RoBERTa / XLM-R).  At most max_positions - pos_offset tokens per row.
+    max_positions: int = 0
+    type_vocab: int = 0
+    pos_offset: int = 0
 
     def __post_init__(self):
         # (a decoder checkpoint names its head_dim: Qwen3's is not hidden / heads)
@@ -64,6 +70,9 @@ class GLiClassConfig:
         if self.kv_heads <= 0:
             object.__setattr__(self, "kv_heads", self.heads)
         assert self.heads % self.kv_heads == 0
+        if self.backbone == BACKBONE_BERT:
+            assert self.head_dim == 64 and self.type_vocab >= 1 and self.pos_offset in (0, self.pad_id + 1)
+            assert self.max_positions - self.pos_offset >= 1
         if self.class_token_index < 0:
             object.__setattr__(self, "class_token_index", self.vocab - 2)
         if self.text_token_index < 0:
@@ -78,6 +87,8 @@ class GLiClassConfig:
         L*S*(4H*nq*d + 4H*nkv*d + 6HI + 4S*nq*d*kappa) + head, kappa = 1/2 when causal; ModernBERT:
         L*S*(8H^2 + 6HI) + sum_l 4*S*H*keys_l + head, keys_l = S on global layers and min(S, 2W+1) on local ones."""
         H, I, L, P = self.hidden, self.inter, self.layers, 2 * self.att_span
+        if self.backbone == BACKBONE_BERT:          # the DeBERTa count without its position projections
+            return L * S * (8 * H * H + 4 * H * I + 4 * S * H) + 8 * H * H * (1 + C)
         if self.backbone == BACKBONE_MODERNBERT:
             keys = sum(S if self.is_global_layer(l) else min(S, 2 * self.local_window + 1) for l in range(L))
             return L * S * (8 * H * H + 6 * H * I) + 4 * S * H * keys + 8 * H * H * (1 + C)
@@ -133,4 +144,12 @@ CONFIGS = {
     "modernbert-large": GLiClassConfig("modernbert-large", vocab=50370, hidden=1024, layers=28, heads=16, inter=2624, ln_eps=1e-5,
                                        backbone=BACKBONE_MODERNBERT, causal=0, rope_theta=160000.0, local_window=64, global_every=3,
                                        rope_theta_local=10000.0),
+    # BERT / RoBERTa / XLM-R backbones: bert-tiny (RoBERTa position ids; H % 256 != 0: the plain paths) and bert-mini (group-split eligible;
+    # a 2050-row position table, one token type) are the parity configs, bert-base the published BERT shape (vocab 30 522)
+    "bert-tiny": GLiClassConfig("bert-tiny", vocab=515, hidden=128, layers=3, heads=2, inter=512, ln_eps=1e-5, pad_id=1, cls_id=0,
+                                backbone=BACKBONE_BERT, causal=0, max_positions=514, type_vocab=2, pos_offset=2),
+    "bert-mini": GLiClassConfig("bert-mini", vocab=1027, hidden=256, layers=4, heads=4, inter=1024, ln_eps=1e-5, pad_id=1, cls_id=0,
+                                backbone=BACKBONE_BERT, causal=0, max_positions=2050, type_vocab=1, pos_offset=2),
+    "bert-base": GLiClassConfig("bert-base", vocab=30522, hidden=768, layers=12, heads=12, inter=3072, ln_eps=1e-12, pad_id=0, cls_id=101,
+                                sep_id=102, backbone=BACKBONE_BERT, causal=0, max_positions=512, type_vocab=2, pos_offset=0),
 }

@@ -124,6 +124,16 @@ template <class T> T* upload_table(glc_engine* e, const std::vector<T>& t, const
 // decoder / ModernBERT: one cos / sin table per (Sp, theta); ModernBERT's global and local layers use two bases
 bool build_rope_tables(glc_engine* e, int Sp) {
     const glc_model_config& c = e->cfg;
+    if (c.backbone == GLC_BACKBONE_BERT) {
+        // no rotation on this backbone: the layout passes get a table of cos = 1, sin = 0 (x 1 - y 0 = x, exact), filed under base 0
+        if (e->ropes.count({Sp, 0.f})) return true;
+        std::vector<float> t((size_t)Sp * (c.head_dim / 2) * 2);
+        for (size_t i = 0; i < t.size(); i += 2) { t[i] = 1.f; t[i + 1] = 0.f; }
+        float* d = upload_table(e, t, "identity rotation table");
+        if (!d) return false;
+        e->ropes[{Sp, 0.f}] = d;
+        return true;
+    }
     const float thetas[2] = {c.rope_theta, c.backbone == GLC_BACKBONE_MODERNBERT ? c.rope_theta_local : c.rope_theta};
     for (float theta : thetas) {
         if (e->ropes.count({Sp, theta})) continue;
@@ -202,14 +212,16 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     }
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     const size_t es = esize(e->dtype);
-    const bool dec = c.backbone == GLC_BACKBONE_DECODER || c.backbone == GLC_BACKBONE_MODERNBERT;    // (same workspace)
+    const bool bert = c.backbone == GLC_BACKBONE_BERT;
+    const bool dec = c.backbone == GLC_BACKBONE_DECODER || c.backbone == GLC_BACKBONE_MODERNBERT || bert;    // (same workspace)
     if (Mpad > e->capM) {
         const size_t rows_h = (size_t)Mpad * c.hidden * es;
         if (!regrow(e, e->X, rows_h) || !regrow(e, e->H1, rows_h) || !regrow(e, e->FF, (size_t)Mpad * c.inter * es) ||
             !regrow(e, e->kbias, (size_t)Mpad * sizeof(float))) return false;
         // (mean, rstd) or (0, rstd) per row of the two residual-stream buffers + the producers' partials (small; DeBERTa keeps them whether or not
         // the fold is switched on: glc_debug_set_ln_fused; the decoder's RMSNorm fold exists in the fp32 mode only)
-        if (!dec || e->dtype == GLC_F32) {
+        if (bert && !regrow(e, e->pos_ids, (size_t)Mpad * sizeof(int))) return false;
+        if ((!dec || e->dtype == GLC_F32) && !bert) {      // (BERT: no norm fold)
             if (!regrow(e, e->statsA, (size_t)Mpad * sizeof(float2)) || !regrow(e, e->statsB, (size_t)Mpad * sizeof(float2)) ||
                 !regrow(e, e->ln_part, (size_t)Mpad * ((c.hidden + 63) / 64) * sizeof(float2))) return false;
         }
@@ -249,7 +261,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     // compact rows of the pruned last layer (every backbone): R = B (1 + C) rows up to the 256-row grid of the small-M GEMMs; the decoder's
     // context rows are heads * head_dim wide, which need not be the hidden size
     const int rsel = round_up(B * (1 + (C > 0 ? C : 0)), 256);
-    if (rsel > e->capSel) {
+    if (rsel > e->capSel && !bert) {       // (BERT: no pruned last layer)
         const size_t wide = dec ? std::max((size_t)c.hidden, (size_t)c.heads * c.head_dim) : (size_t)c.hidden;
         for (void** b : {&e->Xs, &e->CTXs, &e->T1s, &e->H1s}) if (!regrow(e, *b, (size_t)rsel * wide * es)) return false;
         if (!dec && !regrow(e, e->Qs, (size_t)rsel * c.hidden * es)) return false;
@@ -811,6 +823,70 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
     return forward_epilogue(e, e->H1, false, B, S, C, d_logits);
 }
 
+// BERT / RoBERTa / XLM-R backbone (transformers models/bert/modeling_bert.py): one launch sequence per batch.  Post-LayerNorm blocks as
+// DeBERTa's, on the decoder's workspace and attention kernels: word + absolute position + token-type embedding under a LayerNorm (rows.hip
+// embed_abs), then per layer QKV = x Wqkv^T + b, plain bidirectional attention (scores / sqrt(64), additive key mask; the layout pass with a
+// table of cos = 1, sin = 0: no rotation), x = LN1(x + ctx Wo^T + bo), x = LN2(x + gelu_erf(x W1^T + b1) W2^T + b2).  No final norm.
+// 16-bit modes and the fp32 mode's small / odd shapes run plain rows of T; the fp32 mode with H % 256 == 0 runs the group-split pipeline with
+// the norms as kernels of their own (no fold): X, H1, CTX, FF as [32 hi | 32 lo] groups, the residual sums (X2) and QKV plain fp32.  No MX
+// pipeline and no pruned last layer on this backbone.
+bool run_forward_bert(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, nh = c.heads, d = c.head_dim, L = c.layers;
+    const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
+    hipStream_t st = e->stream;
+    const int dt = e->dtype;
+    if (!forward_prologue(e, ids, mask, B, S)) return false;
+    const float qscale = 1.4426950408889634f / sqrtf((float)d);         // head_dim^-1/2, times log2(e) for the exp2 softmax
+    const bool mfma = (dt != GLC_F32 || e->dec_split) && e->attn_impl != 1;
+    bool gs = false;
+    if (dt == GLC_F32 && e->gs_mode > 0 && e->w_presplit && e->dec_split && mfma && !e->keep_hidden && H % 256 == 0 && I % 256 == 0 && L > 0) {
+        GemmArgs t; t.Mpad = Mpad; t.N = H; t.K = H;
+        gs = e->gs_mode == 2 || !glc_gemm_small_m(t);
+    }
+    e->last_gs = gs;
+    e->last_lnf = false; e->last_mx = false; e->last_mx_attn = false; e->last_rope_epi = false; e->last_mx128 = 0; e->last_pruned = false;
+    const GemmGs gemm_gs{st, false, M};
+    { Prof p(e, PC_EMBED);                                                                                   // BertEmbeddings.forward
+      KCHK(glc_launch_pos_ids(st, ids, B, S, Sp, c.pad_id, c.pos_offset, e->pos_ids), false);
+      if (gs) KCHK(glc_launch_embed_abs_gs(st, ids, mask, e->pos_ids, (const float*)e->emb, (const float*)e->pos_emb, (const float*)e->type_emb, e->eln_g, e->eln_b,
+                                           c.ln_eps, e->X, e->kbias, B, S, Sp, H, c.vocab, c.pad_id, c.max_positions), false);
+      else KCHK(glc_launch_embed_abs(st, dt, ids, mask, e->pos_ids, e->emb, e->pos_emb, e->type_emb, e->eln_g, e->eln_b, c.ln_eps, e->X, e->kbias, B, S, Sp, H,
+                                     c.vocab, c.pad_id, c.max_positions), false); }
+    if (!dump_hidden(e, 0, e->X, M)) return false;
+    const float* cs = e->ropes[{Sp, 0.f}];
+    void* T1 = e->X2;                         // the pre-norm sums (plain fp32 in the group-split pipeline)
+    auto norm = [&](void* dst, const float* g, const float* b, bool plain) -> const char* {      // dst = LN(T1)
+        return gs && !plain ? glc_launch_layernorm_gs(st, (const float*)T1, dst, g, b, c.ln_eps, M, H) : glc_launch_layernorm(st, dt, T1, dst, g, b, c.ln_eps, M, H);
+    };
+    for (int l = 0; l < L; ++l) {
+        const LayerW& w = e->layers[l];
+        GemmArgs g;
+        g.A = e->X; g.W = w.Wqkv; g.bias = w.bqkv; g.C = e->QKV; g.Mpad = Mpad; g.N = 3 * H; g.K = H; g.gs_c_plain = 1;
+        { Prof p(e, PC_QKV);
+          KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                                   // BertSelfAttention query / key / value
+          if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);
+          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, cs, M, Sp, nh, nh, d, qscale), false); }
+        { Prof p(e, PC_ATTN);
+          if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, gs ? 1 : 0, 0), false);
+          else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nh, nh, d, 0), false); }
+        GemmArgs o;
+        o.A = e->CTX; o.W = w.Wo; o.bias = w.bo; o.C = T1; o.resid = e->X; o.Mpad = Mpad; o.N = H; o.K = H;
+        { Prof p(e, PC_ATTN_OUT); KCHK(gs ? gemm_gs(EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }      // BertSelfOutput.dense + residual
+        { Prof p(e, PC_LN); KCHK(norm(e->H1, w.ln1g, w.ln1b, false), false); }
+        GemmArgs f1;
+        f1.A = e->H1; f1.W = w.W1; f1.bias = w.b1; f1.C = e->FF; f1.Mpad = Mpad; f1.N = I; f1.K = H;
+        { Prof p(e, PC_FFN1); KCHK(gs ? gemm_gs(EPI_GELU, f1) : launch_gemm_auto(e, dt, EPI_GELU, f1), false); }         // BertIntermediate
+        GemmArgs f2;
+        f2.A = e->FF; f2.W = w.W2; f2.bias = w.b2; f2.C = T1; f2.resid = e->H1; f2.Mpad = Mpad; f2.N = H; f2.K = I;
+        { Prof p(e, PC_FFN2); KCHK(gs ? gemm_gs(EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }       // BertOutput.dense + residual
+        // (the last layer's rows leave the group-split pipeline: the head reads plain fp32 rows)
+        { Prof p(e, PC_LN); KCHK(norm(e->X, w.ln2g, w.ln2b, l == L - 1), false); }
+        if (!dump_hidden(e, l + 1, e->X, M)) return false;
+    }
+    return forward_epilogue(e, e->X, false, B, S, C, d_logits);
+}
+
 // DeBERTa-v3 backbone: one launch sequence per batch (post-norm encoder with disentangled relative-position attention).
 bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
     const glc_model_config& c = e->cfg;
@@ -993,6 +1069,7 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
     switch (e->cfg.backbone) {
     case GLC_BACKBONE_DECODER: return run_forward_decoder(e, ids, mask, B, S, C, d_logits);
     case GLC_BACKBONE_MODERNBERT: return run_forward_modernbert(e, ids, mask, B, S, C, d_logits);
+    case GLC_BACKBONE_BERT: return run_forward_bert(e, ids, mask, B, S, C, d_logits);
     default: return run_forward_deberta(e, ids, mask, B, S, C, d_logits);
     }
 }
@@ -1104,8 +1181,9 @@ bool graph_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B
 size_t staging_floats(const glc_model_config& c) {
     const size_t H = c.hidden, I = c.inter;
     const size_t qkv = c.backbone == GLC_BACKBONE_DECODER ? (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim : 3 * H;
-    const size_t ffn = c.backbone == GLC_BACKBONE_DEBERTA ? I : 2 * I;
-    return std::max({(size_t)c.vocab * H, qkv * H, ffn * H});
+    const size_t ffn = c.backbone == GLC_BACKBONE_DEBERTA || c.backbone == GLC_BACKBONE_BERT ? I : 2 * I;
+    const size_t pos = c.backbone == GLC_BACKBONE_BERT ? (size_t)c.max_positions : 0;
+    return std::max({(size_t)c.vocab * H, qkv * H, ffn * H, pos * H});
 }
 
 // one projection weight: the slot of its device copy and its host row blocks, in order
@@ -1235,6 +1313,32 @@ bool create_modernbert(glc_engine* e, const float* const* tensors, float* stagin
     }
     e->final_norm = upload_f32(e, tensors[L > 0 ? glc_mb_layer_base(L) : 2], H);
     return e->final_norm != nullptr;
+}
+
+// BERT / RoBERTa / XLM-R backbone: upload + convert weights (include/gliclass_hip.h tensor order).  The position table and row 0 of the
+// token-type table (the only row a forward uses: the reference passes no token types) as T beside the word table; per layer the fused
+// Wqkv / bqkv as they come, Wo, W1, W2 with their biases and the two LayerNorms.
+bool create_bert(glc_engine* e, const float* const* tensors, float* staging) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, L = c.layers;
+    const size_t HH = (size_t)H * H, IH = (size_t)I * H, es = esize(e->dtype);
+    e->pos_emb = dmalloc(e, (size_t)c.max_positions * H * es, false);
+    e->type_emb = dmalloc(e, (size_t)H * es, false);
+    if (!e->pos_emb || !e->type_emb || !upload_as(e, tensors[1], (size_t)c.max_positions * H, e->pos_emb, staging) || !upload_as(e, tensors[2], H, e->type_emb, staging)) return false;
+    e->eln_g = upload_f32(e, tensors[3], H); e->eln_b = upload_f32(e, tensors[4], H);
+    if (!e->eln_g || !e->eln_b) return false;
+    e->layers.resize(L);
+    for (int l = 0; l < L; ++l) {
+        const float* const* t = tensors + GLC_BERT_TENSORS_FIXED + GLC_BERT_TENSORS_PER_LAYER * l;
+        LayerW& w = e->layers[l];
+        if (!upload_projections(e, staging, {{&w.Wqkv, {{t[0], 3 * HH}}}, {&w.Wo, {{t[2], HH}}}, {&w.W1, {{t[6], IH}}}, {&w.W2, {{t[8], IH}}}})) return false;
+        w.bqkv = upload_f32(e, t[1], 3 * (size_t)H); w.bo = upload_f32(e, t[3], H);
+        w.ln1g = upload_f32(e, t[4], H); w.ln1b = upload_f32(e, t[5], H);
+        w.b1 = upload_f32(e, t[7], I); w.b2 = upload_f32(e, t[9], H);
+        w.ln2g = upload_f32(e, t[10], H); w.ln2b = upload_f32(e, t[11], H);
+        if (!w.bqkv || !w.bo || !w.ln1g || !w.ln1b || !w.b1 || !w.b2 || !w.ln2g || !w.ln2b) return false;
+    }
+    return true;
 }
 
 // the value a 16-bit MFMA operand carries for f (host side of glc_launch_convert)
@@ -1373,7 +1477,12 @@ bool create_deberta(glc_engine* e, const float* const* tensors, float* staging) 
 bool check_shape(const glc_engine* e, int B, int S, int C) {
     if (B <= 0 || S <= 0 || C < 0) { glc_set_err("forward: B and S must be positive, C non-negative"); return false; }
     if ((long long)B * round_up(S, 64) > (1ll << 30)) { glc_set_err("forward: batch too large"); return false; }
-    (void)e;
+    // BERT backbone: the position table has max_positions rows and the ids start at pos_offset (never a clamp)
+    if (e->cfg.backbone == GLC_BACKBONE_BERT && S > e->cfg.max_positions - e->cfg.pos_offset) {
+        glc_set_err("forward: S = " + std::to_string(S) + " tokens per row, but the position table of this BERT backbone holds max_positions - pos_offset = " +
+                    std::to_string(e->cfg.max_positions - e->cfg.pos_offset));
+        return false;
+    }
     return true;
 }
 
@@ -1415,13 +1524,17 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (cfg->qk_norm && cfg->backbone != GLC_BACKBONE_DECODER) { glc_set_err("engine_create: qk_norm = 1 (per-head RMSNorm on Q and K) exists on the decoder backbone only"); return nullptr; }
     if (n_tensors != glc_num_tensors_cfg(cfg)) { glc_set_err("engine_create: wrong tensor count"); return nullptr; }
     for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { glc_set_err("engine_create: null tensor"); return nullptr; }
-    const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT;
-    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb) { glc_set_err("engine_create: unknown backbone"); return nullptr; }
+    const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT, bert = cfg->backbone == GLC_BACKBONE_BERT;
+    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb && !bert) { glc_set_err("engine_create: unknown backbone"); return nullptr; }
+    if (bert && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64 || cfg->layers < 1 || cfg->type_vocab < 1 || cfg->pos_offset < 0 || cfg->pad_id < 0 ||
+                 cfg->pad_id >= cfg->vocab || (cfg->pos_offset != 0 && cfg->pos_offset != cfg->pad_id + 1) || cfg->max_positions - cfg->pos_offset < 1)) {
+        glc_set_err("engine_create: BERT backbone needs head_dim 64, type_vocab >= 1, pos_offset 0 or pad_id + 1 and max_positions > pos_offset"); return nullptr;
+    }
     if (mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64 || cfg->local_window < 0 || (cfg->local_window > 0 && cfg->global_every < 1) ||
                cfg->rope_theta <= 1.f || (cfg->local_window > 0 && cfg->rope_theta_local <= 1.f))) {
         glc_set_err("engine_create: ModernBERT backbone needs head_dim 64, local_window >= 0, global_every >= 1 and RoPE bases > 1"); return nullptr;
     }
-    if (!dec && !mb && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { glc_set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
+    if (!dec && !mb && !bert && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { glc_set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
     if (dec && ((cfg->head_dim != 64 && cfg->head_dim != 128) || cfg->heads <= 0 || cfg->kv_heads < 0 ||
                 cfg->heads % (cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads) || cfg->rope_theta <= 1.f)) {
         glc_set_err("engine_create: decoder backbone needs head_dim 64 or 128, heads % kv_heads == 0 and rope_theta > 1"); return nullptr;
@@ -1445,7 +1558,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (e->cfg.kv_heads <= 0) e->cfg.kv_heads = e->cfg.heads;
     if (const char* pv = getenv("GLICLASS_PRUNE_LAST")) e->prune_last = atoi(pv) != 0;
     { const char* gv = getenv("GLICLASS_F32_GEMM"); e->w_presplit = !(gv && !strcmp(gv, "native")) ; }   // hidden and inter are multiples of 128 (checked above)
-    { const char* av = getenv("GLICLASS_F32_ATTN"); e->dec_split = dtype == GLC_F32 && (dec || mb) && !(av && !strcmp(av, "native")); }
+    { const char* av = getenv("GLICLASS_F32_ATTN"); e->dec_split = dtype == GLC_F32 && (dec || mb || bert) && !(av && !strcmp(av, "native")); }
     { const char* av = getenv("GLICLASS_F32_ATTN"); e->attn_split = dtype == GLC_F32 && cfg->backbone == GLC_BACKBONE_DEBERTA && !(av && !strcmp(av, "native")); }
     if (const char* lv = glc_dev_env("GLC_LNF")) e->ln_fused = atoi(lv) != 0;      // developer A/B switch
     // MX cross-term pipeline (docs/LOG_r01-r05.md §3e) — the default arithmetic of the large forwards of the default mode since round 3: the
@@ -1457,7 +1570,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
         e->mx_env = !mv ? 0 : !strcmp(mv, "0") ? 1 : !strcmp(mv, "build") ? 2 : 0;
         const bool eligible = dec ? (dtype == GLC_F32 && e->w_presplit && e->dec_split && e->ln_fused && cfg->hidden % 256 == 0 && (2 * cfg->inter) % 256 == 0 && cfg->inter % 32 == 0)
                                   : (dtype == GLC_F32 && e->w_presplit && e->attn_split && e->ln_fused && cfg->hidden % 256 == 0 && cfg->inter % 256 == 0 && cfg->layers >= 2);
-        e->mx_built = eligible && !mb && !(mv && !strcmp(mv, "0"));      // (no MX pipeline for the ModernBERT backbone)
+        e->mx_built = eligible && !mb && !bert && !(mv && !strcmp(mv, "0"));      // (ModernBERT: opt-in, glc_engine_enable_mx; BERT: no MX pipeline)
         e->mx = e->mx_built && !(mv && !strcmp(mv, "build"));
         if (const char* av = glc_dev_env("GLC_MX_ATTN")) e->mx_attn = atoi(av) != 0;      // developer A/B switch
         if (const char* av = glc_dev_env("GLC_DEC_ROPE_EPI")) e->dec_rope_epi = atoi(av) != 0;      // developer A/B switch
@@ -1479,7 +1592,8 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     const size_t nemb = (size_t)cfg->vocab * H;           // the token embeddings (HF:518-562)
     e->emb = dmalloc(e, nemb * esize(dtype), false);
     if (!e->emb || !upload_as(e, tensors[0], nemb, e->emb, staging)) return fail();
-    const bool loaded = dec ? create_decoder(e, tensors, staging) : mb ? create_modernbert(e, tensors, staging) : create_deberta(e, tensors, staging);
+    const bool loaded = dec ? create_decoder(e, tensors, staging) : mb ? create_modernbert(e, tensors, staging) : bert ? create_bert(e, tensors, staging)
+                                                                                                                  : create_deberta(e, tensors, staging);
     if (!loaded || !upload_head(e, tensors + n_tensors - GLC_TENSORS_HEAD - glc_num_scorer_tensors(cfg->scorer))) return fail();
     // ModernBERT: the MX pipeline is opt-in; the environment makes the call glc_engine_enable_mx documents (read once, here).  An engine it does
     // not fit stays as it is: not an error.
@@ -1503,6 +1617,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
 int glc_engine_enable_mx(glc_engine* e) {
     if (!e) { glc_set_err("enable_mx: null engine"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
+    if (e->cfg.backbone == GLC_BACKBONE_BERT) { glc_set_err("enable_mx: the BERT backbone has no MX pipeline (its forwards run the split-f16 / 16-bit kernels)"); return -1; }
     if (e->cfg.backbone != GLC_BACKBONE_MODERNBERT) {
         if (e->mx_built) return 0;
         glc_set_err("enable_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1;
@@ -1974,7 +2089,7 @@ int glc_engine_set_mx_small_forwards(glc_engine* e, int mode) {
     if (mode < 0 || mode > 2) { glc_set_err("set_mx_small_forwards: 0 off, 1 auto, 2 whenever the shapes allow"); return -1; }
     if (mode > 0 && e->cfg.backbone != GLC_BACKBONE_DEBERTA) {
         glc_set_err(std::string("set_mx_small_forwards: the 128 tile has no epilogue of the ") +
-                    (e->cfg.backbone == GLC_BACKBONE_DECODER ? "decoder" : "modernbert") + " backbone (DeBERTa engines only)");
+                    (e->cfg.backbone == GLC_BACKBONE_DECODER ? "decoder" : e->cfg.backbone == GLC_BACKBONE_BERT ? "bert" : "modernbert") + " backbone (DeBERTa engines only)");
         return -1;
     }
     std::lock_guard<std::mutex> lk(e->mu);

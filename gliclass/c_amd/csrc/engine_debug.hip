@@ -86,6 +86,16 @@ int glc_debug_read_workspace(glc_engine* e, int which, int rows, float* out) {
     return 0;
 }
 
+int glc_debug_read_pos_ids(glc_engine* e, int32_t* out, int n) {
+    if (!e || !out || n <= 0) { glc_set_err("read_pos_ids: bad args"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->cfg.backbone != GLC_BACKBONE_BERT || !e->pos_ids || n != e->lastB * e->lastSp) { glc_set_err("read_pos_ids: a BERT engine's last forward has B * Sp ids"); return -1; }
+    HIPCHK(hipSetDevice(e->device), -1);
+    HIPCHK(hipStreamSynchronize(e->stream), -1);
+    HIPCHK(hipMemcpy(out, e->pos_ids, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), -1);
+    return 0;
+}
+
 int glc_debug_get_hidden(glc_engine* e, int which, float* out, size_t out_elems) {
     if (!e || !out) { glc_set_err("get_hidden: null"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);

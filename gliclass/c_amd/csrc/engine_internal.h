@@ -140,6 +140,9 @@ struct glc_engine {
     std::vector<LayerW> layers;
     std::vector<DecLayerW> dlayers; float* final_norm = nullptr;      // decoder backbone; ModernBERT: Wgu = Wi, Wd = mlp.Wo, ln1 / ln2 = attn_norm / mlp_norm
     float* zero_bias = nullptr;                                       // ModernBERT: [H] zeros, the beta of its bias-free LayerNorms
+    // BERT backbone (layers, eln_g / eln_b as DeBERTa's; the decoder's workspace): the position table [max_positions, H] and row 0 of the
+    // token-type table as T, and the position ids [capM] of the forward (rows.hip pos_ids_kernel)
+    void *pos_emb = nullptr, *type_emb = nullptr; int* pos_ids = nullptr;
     std::map<std::pair<int, float>, float*> ropes;                    // (Sp, theta) -> [Sp][d/2][cos,sin]
     void *QKV = nullptr, *GU = nullptr, *X2 = nullptr;                // decoder workspace: fused QKV rows, [gate|up] rows, second residual buffer
     bool fused_swiglu = false;                                        // Wgu rows interleaved 16 gate / 16 up: SwiGLU runs in the GEMM epilogue

@@ -178,6 +178,18 @@ const char* glc_launch_gemm256s_gs(hipStream_t st, int epi, const GemmArgs& a);
 const char* glc_launch_embed(hipStream_t st, int dtype, const int64_t* ids, const int64_t* mask, const void* table,
                              const float* gamma, const float* beta, float eps, void* X, float* kbias,
                              int B, int S, int Sp, int H, int vocab, int pad_id);
+// BERT / RoBERTa / XLM-R backbone (modeling_bert.py BertEmbeddings): position ids of the padded [B, Sp] grid — pos_offset == 0: s; else
+// (create_position_ids_from_input_ids) the inclusive count of ids != pad_id up to s, plus pad_id, for a non-pad token and pad_id for a pad
+// token; slack positions s >= S name a row that exists — then X[b*Sp + s, :] = LN(word[id] + position[pos] + type0) * gamma + beta as rows
+// of T (glc_launch_embed_abs) or as group-split rows of the fp32 mode (glc_launch_embed_abs_gs; fp32 tables), rows s >= S zero, and
+// kbias as glc_launch_embed writes it.  type0 = row 0 of the token-type table; max_pos = rows of the position table (pos is clamped to it).
+const char* glc_launch_pos_ids(hipStream_t st, const int64_t* ids, int B, int S, int Sp, int pad_id, int pos_offset, int* pos_ids);
+const char* glc_launch_embed_abs(hipStream_t st, int dtype, const int64_t* ids, const int64_t* mask, const int* pos_ids, const void* word, const void* ptab,
+                                 const void* type0, const float* gamma, const float* beta, float eps, void* X, float* kbias, int B, int S, int Sp,
+                                 int H, int vocab, int pad_id, int max_pos);
+const char* glc_launch_embed_abs_gs(hipStream_t st, const int64_t* ids, const int64_t* mask, const int* pos_ids, const float* word, const float* ptab,
+                                    const float* type0, const float* gamma, const float* beta, float eps, void* X, float* kbias, int B, int S, int Sp,
+                                    int H, int vocab, int pad_id, int max_pos);
 
 // Per batch row: klen[b] = 1 + last valid key (0 if none), kfirst[b] = first masked key (S if none); ordered positions of class tokens
 // cls_pos[b*c_cap + j] (-1 beyond the row's count) and cls_cnt[b].

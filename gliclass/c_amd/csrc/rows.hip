@@ -227,6 +227,161 @@ __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ 
     ln_row_wave<T, true>(table + (size_t)id * H, X + (size_t)row * H, gamma, beta, eps, H, mk, lane);
 }
 
+// ---- BERT / RoBERTa / XLM-R backbone: position ids and the absolute-position embedding (modeling_bert.py BertEmbeddings,
+// modeling_roberta.py create_position_ids_from_input_ids) ----
+// Position ids of the padded [B, Sp] grid, one workgroup per batch row.  pos_offset == 0 (BERT): pos = s.  Otherwise (RoBERTa / XLM-R,
+// pos_offset = pad_id + 1): pos = (inclusive count of ids != pad_id up to s) + pad_id for a non-pad token, pad_id for a pad token.  Each
+// thread counts a contiguous piece of the row, the counts are scanned with wavefront shuffles and the four wave totals go through LDS.
+// Slack positions s >= S get a row that exists (pad_id, or 0 for BERT): the embedding kernel zeroes them.
+__global__ __launch_bounds__(256) void pos_ids_kernel(const int64_t* __restrict__ ids, int S, int Sp, int pad_id, int pos_offset, int* __restrict__ pos) {
+    __shared__ int wtot[4];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int* out = pos + (size_t)b * Sp;
+    if (pos_offset == 0) {                       // (uniform over the grid)
+        for (int s = t; s < Sp; s += 256) out[s] = s < S ? s : 0;
+        return;
+    }
+    const int64_t* row = ids + (size_t)b * S;
+    const int per = (S + 255) / 256;
+    const int lo = min(S, t * per), hi = min(S, lo + per);
+    int c = 0;
+    for (int s = lo; s < hi; ++s) c += row[s] != pad_id;
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
+    if (lane == 63) wtot[wv] = incl;
+    __syncthreads();
+    int run = incl - c;
+    for (int w = 0; w < wv; ++w) run += wtot[w];
+    for (int s = lo; s < hi; ++s) {
+        const bool tok = row[s] != pad_id;
+        run += tok;
+        out[s] = tok ? run + pad_id : pad_id;
+    }
+    for (int s = S + t; s < Sp; s += 256) out[s] = pad_id;
+}
+
+// One wave per row of the padded [B, Sp] grid: x = word[id] + position[pos] + type[0] in fp32, LayerNorm with gain and bias, the row as T.
+// Rows s < S are written whether attended or not (HF does not mask the embedding output; a masked token is masked as a key, by kbias);
+// slack rows s >= S are zero.  pos is clamped to the table: a row the table does not have is never read.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_abs_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, const int* __restrict__ pos_ids,
+                                                        const T* __restrict__ word, const T* __restrict__ ptab, const T* __restrict__ type0,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps, T* __restrict__ X,
+                                                        float* __restrict__ kbias, int B, int S, int Sp, int H, int vocab, int pad_id, int max_pos) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B * Sp) return;
+    const int lane = threadIdx.x & 63;
+    const int b = row / Sp, s = row - b * Sp;
+    long long id = pad_id;
+    float mk = 0.f;
+    if (s < S) {
+        id = ids[(size_t)b * S + s];
+        mk = mask[(size_t)b * S + s] != 0 ? 1.f : 0.f;
+        if (id < 0 || id >= vocab) id = pad_id;
+    }
+    if (lane == 0) kbias[row] = mk != 0.f ? 0.f : GLC_NEG_BIG;
+    const int p = min(max(pos_ids[row], 0), max_pos - 1);
+    constexpr int VEC = RowVec<T>::VEC;
+    typedef __attribute__((ext_vector_type(VEC))) T vecT;
+    const T* w = word + (size_t)id * H;
+    const T* q = ptab + (size_t)p * H;
+    T* y = X + (size_t)row * H;
+    const int nch = H / VEC;
+    float v[MAXC][VEC];
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nch) {
+            const vecT a = *reinterpret_cast<const vecT*>(w + (size_t)ch * VEC), pp = *reinterpret_cast<const vecT*>(q + (size_t)ch * VEC),
+                       tt = *reinterpret_cast<const vecT*>(type0 + (size_t)ch * VEC);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) { v[c][e] = (float)a[e] + (float)tt[e] + (float)pp[e]; sum += v[c][e]; }      // BertEmbeddings: (word + type) + position
+        }
+    }
+    const float mean = wave_sum(sum) / (float)H;
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        if (lane + 64 * c < nch) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) { const float d = v[c][e] - mean; ss += d * d; }
+        }
+    }
+    const float rstd = rsqrtf(wave_sum(ss) / (float)H + eps);
+    const float live = s < S ? 1.f : 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nch) {
+            vecT o;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o[e] = (T)(((v[c][e] - mean) * rstd * gamma[ch * VEC + e] + beta[ch * VEC + e]) * live);
+            *reinterpret_cast<vecT*>(y + (size_t)ch * VEC) = o;
+        }
+    }
+}
+// ... and its group-split form (fp32 mode): the same row as [32 hi | 32 lo] f16 groups
+__global__ __launch_bounds__(256) void embed_abs_gs_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, const int* __restrict__ pos_ids,
+                                                           const float* __restrict__ word, const float* __restrict__ ptab, const float* __restrict__ type0,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps, f16_t* __restrict__ X,
+                                                           float* __restrict__ kbias, int B, int S, int Sp, int H, int vocab, int pad_id, int max_pos) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= B * Sp) return;
+    const int lane = threadIdx.x & 63;
+    const int b = row / Sp, s = row - b * Sp;
+    long long id = pad_id;
+    float mk = 0.f;
+    if (s < S) {
+        id = ids[(size_t)b * S + s];
+        mk = mask[(size_t)b * S + s] != 0 ? 1.f : 0.f;
+        if (id < 0 || id >= vocab) id = pad_id;
+    }
+    if (lane == 0) kbias[row] = mk != 0.f ? 0.f : GLC_NEG_BIG;
+    const int p = min(max(pos_ids[row], 0), max_pos - 1);
+    const float* w = word + (size_t)id * H;
+    const float* q = ptab + (size_t)p * H;
+    f16_t* y = X + (size_t)row * 2 * H;
+    const int nch = H / 8;
+    float v[MAXC][8];
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nch) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(w + (size_t)ch * 8 + 4 * h), pp = *reinterpret_cast<const f32x4*>(q + (size_t)ch * 8 + 4 * h),
+                            tt = *reinterpret_cast<const f32x4*>(type0 + (size_t)ch * 8 + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { v[c][4 * h + e] = a[e] + tt[e] + pp[e]; sum += v[c][4 * h + e]; }
+            }
+        }
+    }
+    const float mean = wave_sum(sum) / (float)H;
+    float ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        if (lane + 64 * c < nch) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { const float d = v[c][e] - mean; ss += d * d; }
+        }
+    }
+    const float rstd = rsqrtf(wave_sum(ss) / (float)H + eps);
+    const float live = s < S ? 1.f : 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {
+        const int ch = lane + 64 * c;
+        if (ch < nch) {
+            float o[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = ((v[c][e] - mean) * rstd * gamma[ch * 8 + e] + beta[ch * 8 + e]) * live;
+            gs_store8(y, ch * 8, o);
+        }
+    }
+}
+
 // one block per batch row; ordered compaction of class-token positions by a block-wide scan
 __global__ __launch_bounds__(256) void scan_rows_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask, int S,
                                                         int class_token, int embed_class_token, int* __restrict__ klen,
@@ -502,6 +657,38 @@ const char* glc_launch_embed_gs(hipStream_t st, const int64_t* ids, const int64_
     if (H <= 0 || H % 32 || H / 8 > 64 * MAXC) return "embed_gs: unsupported hidden size";
     if (gx) hipLaunchKernelGGL(embed_gs_kernel<true>, dim3((B * Sp + 3) / 4), dim3(256), 0, st, ids, mask, table, gamma, beta, eps, (f16_t*)X, kbias, B, S, Sp, H, vocab, pad_id, glc_gx_sat_ptr(), glc_gx_act_sc());
     else hipLaunchKernelGGL(embed_gs_kernel<false>, dim3((B * Sp + 3) / 4), dim3(256), 0, st, ids, mask, table, gamma, beta, eps, (f16_t*)X, kbias, B, S, Sp, H, vocab, pad_id, (unsigned*)nullptr, 0);
+    return nullptr;
+}
+
+const char* glc_launch_pos_ids(hipStream_t st, const int64_t* ids, int B, int S, int Sp, int pad_id, int pos_offset, int* pos_ids) {
+    if (B <= 0 || S <= 0 || Sp < S || !ids || !pos_ids || pad_id < 0 || pos_offset < 0) return "pos_ids: bad args";
+    hipLaunchKernelGGL(pos_ids_kernel, dim3(B), dim3(256), 0, st, ids, S, Sp, pad_id, pos_offset, pos_ids);
+    return nullptr;
+}
+
+const char* glc_launch_embed_abs(hipStream_t st, int dtype, const int64_t* ids, const int64_t* mask, const int* pos_ids, const void* word, const void* ptab,
+                                 const void* type0, const float* gamma, const float* beta, float eps, void* X, float* kbias, int B, int S, int Sp,
+                                 int H, int vocab, int pad_id, int max_pos) {
+    if (B <= 0 || S <= 0 || Sp < S || !ids || !mask || !pos_ids || !word || !ptab || !type0 || !gamma || !beta || !X || !kbias) return "embed_abs: bad args";
+    if (pad_id < 0 || pad_id >= vocab) return "embed_abs: pad id outside vocab";
+    if (max_pos <= 0) return "embed_abs: empty position table";
+    DISPATCH_T(dtype, {
+        if (!h_ok<T>(H)) return "embed_abs: unsupported hidden size";
+        hipLaunchKernelGGL(embed_abs_kernel<T>, dim3((B * Sp + 3) / 4), dim3(256), 0, st, ids, mask, pos_ids, (const T*)word, (const T*)ptab, (const T*)type0,
+                           gamma, beta, eps, (T*)X, kbias, B, S, Sp, H, vocab, pad_id, max_pos);
+    });
+    return nullptr;
+}
+
+const char* glc_launch_embed_abs_gs(hipStream_t st, const int64_t* ids, const int64_t* mask, const int* pos_ids, const float* word, const float* ptab,
+                                    const float* type0, const float* gamma, const float* beta, float eps, void* X, float* kbias, int B, int S, int Sp,
+                                    int H, int vocab, int pad_id, int max_pos) {
+    if (B <= 0 || S <= 0 || Sp < S || !ids || !mask || !pos_ids || !word || !ptab || !type0 || !gamma || !beta || !X || !kbias) return "embed_abs_gs: bad args";
+    if (pad_id < 0 || pad_id >= vocab) return "embed_abs_gs: pad id outside vocab";
+    if (max_pos <= 0) return "embed_abs_gs: empty position table";
+    if (H <= 0 || H % 32 || H / 8 > 64 * MAXC) return "embed_abs_gs: unsupported hidden size";
+    hipLaunchKernelGGL(embed_abs_gs_kernel, dim3((B * Sp + 3) / 4), dim3(256), 0, st, ids, mask, pos_ids, word, ptab, type0, gamma, beta, eps, (f16_t*)X, kbias,
+                       B, S, Sp, H, vocab, pad_id, max_pos);
     return nullptr;
 }
 

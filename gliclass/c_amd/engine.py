@@ -17,7 +17,7 @@ def to_c_config(cfg: GLiClassConfig) -> _lib.ModelConfig:
                             cfg.max_rel_pos, cfg.pad_id, cfg.cls_id, cfg.sep_id, cfg.class_token_index, cfg.text_token_index,
                             cfg.pooling, cfg.scorer, cfg.embed_class_token, cfg.normalize_features, cfg.backbone, cfg.kv_heads,
                             cfg.causal, cfg.ln_eps, cfg.logit_scale, cfg.rope_theta, cfg.local_window, cfg.global_every,
-                            cfg.rope_theta_local, cfg.qk_norm, cfg.attn_bias)
+                            cfg.rope_theta_local, cfg.qk_norm, cfg.attn_bias, cfg.max_positions, cfg.type_vocab, cfg.pos_offset)
 
 
 def delta_table(S, bucket_size=256, max_position=512):
@@ -187,6 +187,14 @@ class Engine:
     def range_retries(self):
         """host-buffer forwards repeated with the norms unfused because the folded forward came out non-finite"""
         return int(self.L.glc_debug_range_retries(self.h))
+
+    def pos_ids(self, B, S):
+        """BERT backbone: the position ids [B, Sp] of the last forward (Sp = S rounded up to 64), as the embedding kernel read them"""
+        Sp = (S + 63) // 64 * 64
+        out = np.zeros((B, Sp), np.int32)
+        if self.L.glc_debug_read_pos_ids(self.h, out.ctypes.data, out.size) != 0:
+            raise self._err("glc_debug_read_pos_ids")
+        return out
 
     def keep_hidden(self, on=True):
         self.L.glc_debug_keep_hidden(self.h, int(on))

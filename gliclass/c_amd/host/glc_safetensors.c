@@ -6,7 +6,8 @@
  * config.json and the safetensors header (8-byte little-endian length, JSON {"name": {"dtype","shape","data_offsets"}},
  * raw little-endian tensor data); F32 / F16 / BF16 tensors are widened to fp32.
  *
- * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `Qwen3Model` / `LlamaModel` / `ModernBertModel` state_dict) under any of the prefixes GLiClass checkpoints use;
+ * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `Qwen3Model` / `LlamaModel` / `ModernBertModel` / `BertModel` / `RobertaModel` state_dict) under any of the prefixes GLiClass checkpoints use
+ * (the BERT family's query / key / value projections are concatenated into the fused Wqkv of the tensor order);
  * configuration fields follow transformers' DebertaV2Config / Qwen2Config inside `encoder_config`, and the GLiClass
  * fields as restated in SURVEY.md §8a row a12 (class_token_index, text_token_index, pooling_strategy, scorer_type,
  * embed_class_token, normalize_features ...).  The GLiClass field names come from the upstream python package, which
@@ -26,7 +27,9 @@
 
 static const char* const kPrefixes[] = {"", "model.", "deberta.", "encoder_model.model.", "model.encoder_model.model.",
                                         "encoder_model.", "model.encoder_model.", "decoder_model.model.", "model.decoder_model.model.",
-                                        "encoder_model.deberta.", "model.encoder_model.deberta."};
+                                        "encoder_model.deberta.", "model.encoder_model.deberta.",
+                                        "bert.", "roberta.", "encoder_model.bert.", "encoder_model.roberta.", "model.encoder_model.bert.",
+                                        "model.encoder_model.roberta."};
 #define N_PREFIXES (sizeof(kPrefixes) / sizeof(kPrefixes[0]))
 
 static double jnum(const gj_value* o, const char* k, double dflt) {
@@ -214,7 +217,29 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
             const char* rs = gj_is(sa, GJ_OBJ) ? jtext(sa, "rope_type") : NULL;
             if ((rt && strcmp(rt, "default")) || (rs && strcmp(rs, "default"))) REJECT("rope_type other than 'default' is not implemented");
         }
-    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, qwen3, llama, modernbert)", mt);
+    } else if (!strcmp(mt, "bert") || !strcmp(mt, "roberta") || !strcmp(mt, "xlm-roberta")) {
+        /* transformers models/bert, models/roberta, models/xlm_roberta: one arithmetic; RoBERTa / XLM-R number the non-pad tokens from
+         * pad_token_id + 1 on (create_position_ids_from_input_ids), BERT numbers the positions from 0 */
+        const int is_bert = !strcmp(mt, "bert");
+        c->backbone = GLC_BACKBONE_BERT;
+        c->kv_heads = c->heads; c->causal = 0; c->rope_theta = 1.0e6f; c->global_every = 1; c->rope_theta_local = 1.0e4f;
+        c->pos_buckets = 0; c->max_rel_pos = 0;
+        c->ln_eps = (float)jnum(enc, "layer_norm_eps", 1e-12);
+        c->pad_id = (int32_t)jnum(enc, "pad_token_id", is_bert ? 0 : 1);
+        const char* pet = jtext(enc, "position_embedding_type");
+        if (pet && strcmp(pet, "absolute")) REJECT("position_embedding_type '%s' is not implemented (absolute)", pet);
+        const char* act = jtext(enc, "hidden_act");
+        if (act && strcmp(act, "gelu")) REJECT("hidden_act '%s' is not implemented (gelu)", act);
+        if (jflag(enc, "is_decoder", 0)) REJECT("is_decoder=true is not implemented");
+        if (jflag(enc, "add_cross_attention", 0)) REJECT("add_cross_attention=true is not implemented");
+        if (c->head_dim != 64) REJECT("head_dim %d is not implemented (64)", c->head_dim);
+        c->pos_offset = is_bert ? 0 : c->pad_id + 1;
+        c->max_positions = (int32_t)jnum(enc, "max_position_embeddings", 512);
+        c->type_vocab = (int32_t)jnum(enc, "type_vocab_size", 2);
+        if (c->pad_id < 0) REJECT("pad_token_id %d is negative", c->pad_id);
+        if (c->max_positions - c->pos_offset < 1) REJECT("max_position_embeddings %d leaves no position behind the offset %d", c->max_positions, c->pos_offset);
+        if (c->type_vocab < 1) REJECT("type_vocab_size %d is not implemented (at least 1)", c->type_vocab);
+    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, qwen3, llama, modernbert, bert, roberta, xlm-roberta)", mt);
     return 0;
 }
 
@@ -237,6 +262,30 @@ static float half_to_float(uint16_t h) {
     } else if (exp == 31) bits = sign | 0x7F800000u | (man << 13);
     else bits = sign | ((exp + 112u) << 23) | (man << 13);
     float f; memcpy(&f, &bits, 4); return f;
+}
+
+/* tensor `name` (under any known prefix) with the shape shp[0 .. nd) -> n fp32 values at dst; F32 / F16 / BF16 are read.  0, or -1 with a message */
+static int st_read_f32(const st_file* st, const char* stp, const char* name, int nd, const uint64_t* shp, float* dst) {
+    char found[200];
+    const size_t n = (size_t)shp[0] * (nd > 1 ? (size_t)shp[1] : 1);
+    const gj_value* t = st_find(st, name, found, sizeof found);
+    if (!t) { fprintf(stderr, "Error: '%s': tensor '%s' not found under any known prefix\n", stp, name); return -1; }
+    const char* dt = jtext(t, "dtype");
+    const gj_value* shape = gj_get(t, "shape");
+    const gj_value* offs = gj_get(t, "data_offsets");
+    if (!dt || !gj_is(shape, GJ_ARR) || !gj_is(offs, GJ_ARR) || offs->u.arr.n != 2) { fprintf(stderr, "Error: '%s': malformed entry '%s'\n", stp, found); return -1; }
+    int shape_ok = (int)shape->u.arr.n == nd;
+    for (int d = 0; shape_ok && d < nd; ++d) shape_ok = (uint64_t)shape->u.arr.items[d]->u.num == shp[d];
+    if (!shape_ok) { fprintf(stderr, "Error: '%s': tensor '%s' has an unexpected shape (want %llu x %llu)\n", stp, found, (unsigned long long)shp[0], (unsigned long long)(nd > 1 ? shp[1] : 1)); return -1; }
+    size_t b0 = (size_t)offs->u.arr.items[0]->u.num, b1 = (size_t)offs->u.arr.items[1]->u.num;
+    size_t esz = !strcmp(dt, "F32") ? 4 : (!strcmp(dt, "F16") || !strcmp(dt, "BF16")) ? 2 : 0;
+    if (!esz) { fprintf(stderr, "Error: '%s': tensor '%s' has dtype %s (F32, F16, BF16 are read)\n", stp, found, dt); return -1; }
+    if (b1 < b0 || b1 > st->data_len || b1 - b0 != n * esz) { fprintf(stderr, "Error: '%s': tensor '%s' has bad data offsets\n", stp, found); return -1; }
+    const unsigned char* src = st->data + b0;
+    if (esz == 4) memcpy(dst, src, n * 4);
+    else if (dt[0] == 'B') for (size_t k = 0; k < n; ++k) { uint32_t u = ((uint32_t)src[2 * k] | ((uint32_t)src[2 * k + 1] << 8)) << 16; memcpy(&dst[k], &u, 4); }
+    else for (size_t k = 0; k < n; ++k) dst[k] = half_to_float((uint16_t)(src[2 * k] | (src[2 * k + 1] << 8)));
+    return 0;
 }
 
 int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
@@ -321,25 +370,25 @@ int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
     for (int i = 0; i < w->n_tensors; ++i) {
         int nd = glc_tensor_spec(c, i, tn, shp, &amp, &mean);
         size_t n = (size_t)shp[0] * (nd > 1 ? (size_t)shp[1] : 1);
-        const gj_value* t = st_find(&st, tn, found, sizeof found);
-        if (!t) { fprintf(stderr, "Error: '%s': tensor '%s' not found under any known prefix\n", stp, tn); goto done; }
-        const char* dt = jtext(t, "dtype");
-        const gj_value* shape = gj_get(t, "shape");
-        const gj_value* offs = gj_get(t, "data_offsets");
-        if (!dt || !gj_is(shape, GJ_ARR) || !gj_is(offs, GJ_ARR) || offs->u.arr.n != 2) { fprintf(stderr, "Error: '%s': malformed entry '%s'\n", stp, found); goto done; }
-        int shape_ok = (int)shape->u.arr.n == nd;
-        for (int d = 0; shape_ok && d < nd; ++d) shape_ok = (uint64_t)shape->u.arr.items[d]->u.num == shp[d];
-        if (!shape_ok) { fprintf(stderr, "Error: '%s': tensor '%s' has an unexpected shape (want %llu x %llu)\n", stp, found, (unsigned long long)shp[0], (unsigned long long)(nd > 1 ? shp[1] : 1)); goto done; }
-        size_t b0 = (size_t)offs->u.arr.items[0]->u.num, b1 = (size_t)offs->u.arr.items[1]->u.num;
-        size_t esz = !strcmp(dt, "F32") ? 4 : (!strcmp(dt, "F16") || !strcmp(dt, "BF16")) ? 2 : 0;
-        if (!esz) { fprintf(stderr, "Error: '%s': tensor '%s' has dtype %s (F32, F16, BF16 are read)\n", stp, found, dt); goto done; }
-        if (b1 < b0 || b1 > st.data_len || b1 - b0 != n * esz) { fprintf(stderr, "Error: '%s': tensor '%s' has bad data offsets\n", stp, found); goto done; }
-        float* dst = w->_owned + off;
-        const unsigned char* src = st.data + b0;
-        if (esz == 4) memcpy(dst, src, n * 4);
-        else if (dt[0] == 'B') for (size_t k = 0; k < n; ++k) { uint32_t u = ((uint32_t)src[2 * k] | ((uint32_t)src[2 * k + 1] << 8)) << 16; memcpy(&dst[k], &u, 4); }
-        else for (size_t k = 0; k < n; ++k) dst[k] = half_to_float((uint16_t)(src[2 * k] | (src[2 * k + 1] << 8)));
-        w->tensors[i] = dst;
+        /* BERT family: the fused Wqkv rows (and bias) are the checkpoint's query | key | value tensors, one after the other */
+        const char* fq = c->backbone == GLC_BACKBONE_BERT ? strstr(tn, ".attention.self.Wqkv.") : NULL;
+        if (fq) {
+            static const char* const part[3] = {"query", "key", "value"};
+            const uint64_t prow = shp[0] / 3;
+            int bad = 0;
+            for (int q = 0; q < 3 && !bad; ++q) {
+                char pn[128];
+                snprintf(pn, sizeof pn, "%.*s.attention.self.%s.%s", (int)(fq - tn), tn, part[q], fq + strlen(".attention.self.Wqkv."));
+                uint64_t pshp[2] = {prow, nd > 1 ? shp[1] : 0};
+                if (st_read_f32(&st, stp, pn, nd, pshp, w->_owned + off + (size_t)q * (n / 3))) bad = 1;
+            }
+            if (bad) goto done;
+            w->tensors[i] = w->_owned + off;
+            off += (n + 15) / 16 * 16;
+            continue;
+        }
+        if (st_read_f32(&st, stp, tn, nd, shp, w->_owned + off)) goto done;
+        w->tensors[i] = w->_owned + off;
         off += (n + 15) / 16 * 16;
     }
     rc = 0;

@@ -96,6 +96,25 @@ int glc_named_config(const char* name, glc_model_config* c) {
             c->local_window = MB[i].window; c->global_every = 3; c->rope_theta_local = 10000.0f; c->attn_bias = 1;
             return 0;
         }
+    /* BERT / RoBERTa / XLM-R backbones (config.py CONFIGS "bert-tiny", "bert-mini": RoBERTa position ids; "bert-base": the published BERT shape) */
+    static const struct { const char* n; int vocab, hidden, layers, heads, inter, maxpos, types, off, pad, cls, sep; float eps; } BT[] = {
+        {"bert-tiny", 515, 128, 3, 2, 512, 514, 2, 2, 1, 0, 2, 1e-5f},   {"bert-mini", 1027, 256, 4, 4, 1024, 2050, 1, 2, 1, 0, 2, 1e-5f},
+        {"bert-base", 30522, 768, 12, 12, 3072, 512, 2, 0, 0, 101, 102, 1e-12f},
+    };
+    for (size_t i = 0; i < sizeof(BT) / sizeof(BT[0]); ++i)
+        if (strcmp(name, BT[i].n) == 0) {
+            memset(c, 0, sizeof(*c));
+            c->vocab = BT[i].vocab; c->hidden = BT[i].hidden; c->layers = BT[i].layers; c->heads = BT[i].heads;
+            c->head_dim = 64; c->inter = BT[i].inter; c->pos_buckets = 256; c->max_rel_pos = 512;
+            c->pad_id = BT[i].pad; c->cls_id = BT[i].cls; c->sep_id = BT[i].sep;
+            c->class_token_index = c->vocab - 2; c->text_token_index = c->vocab - 1;
+            c->pooling = GLC_POOL_FIRST; c->scorer = GLC_SCORER_DOT; c->embed_class_token = 1; c->normalize_features = 0;
+            c->backbone = GLC_BACKBONE_BERT; c->kv_heads = c->heads; c->causal = 0; c->rope_theta = 1.0e6f;
+            c->ln_eps = BT[i].eps; c->logit_scale = 1.0f;
+            c->global_every = 1; c->rope_theta_local = 1.0e4f; c->attn_bias = 1;
+            c->max_positions = BT[i].maxpos; c->type_vocab = BT[i].types; c->pos_offset = BT[i].off;
+            return 0;
+        }
     return -1;
 }
 
@@ -173,6 +192,37 @@ int glc_tensor_spec(const glc_model_config* c, int i, char* name, uint64_t shape
         }
         if (i == nend) SPEC1("final_norm.weight", H, 0.2, 1.0);
         return head_spec(c, i - nend - 1, name, shape, amp, mean);
+    }
+    if (c->backbone == GLC_BACKBONE_BERT) {             /* include/gliclass_hip.h; mirrors weights.tensor_specs */
+        char buf[96];
+        switch (i) {
+            case 0: SPEC2("embeddings.word_embeddings.weight", (uint64_t)c->vocab, H, 1.0);
+            case 1: SPEC2("embeddings.position_embeddings.weight", (uint64_t)c->max_positions, H, 0.5);
+            case 2: snprintf(name, 96, "%s", "embeddings.token_type_embeddings.weight"); shape[0] = (uint64_t)c->type_vocab; shape[1] = H; *amp = 0.3; *mean = 0.1; return 2;
+            case 3: SPEC1("embeddings.LayerNorm.weight", H, 0.2, 1.0);
+            case 4: SPEC1("embeddings.LayerNorm.bias", H, 0.1, 0.0);
+            default: break;
+        }
+        const int nl = GLC_BERT_TENSORS_PER_LAYER * c->layers;
+        if (i >= GLC_BERT_TENSORS_FIXED && i < GLC_BERT_TENSORS_FIXED + nl) {
+            const int l = (i - GLC_BERT_TENSORS_FIXED) / GLC_BERT_TENSORS_PER_LAYER, k = (i - GLC_BERT_TENSORS_FIXED) % GLC_BERT_TENSORS_PER_LAYER;
+            static const char* sfx[12] = {
+                "attention.self.Wqkv.weight", "attention.self.Wqkv.bias", "attention.output.dense.weight", "attention.output.dense.bias",
+                "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias", "intermediate.dense.weight", "intermediate.dense.bias",
+                "output.dense.weight", "output.dense.bias", "output.LayerNorm.weight", "output.LayerNorm.bias"};
+            snprintf(buf, sizeof buf, "encoder.layer.%d.%s", l, sfx[k]);
+            switch (k) {
+                case 0: SPEC2(buf, 3 * H, H, lin_amp(1.6, (double)H));
+                case 1: SPEC1(buf, 3 * H, 0.1, 0.0);
+                case 2: SPEC2(buf, H, H, lin_amp(1.0, (double)H));
+                case 6: SPEC2(buf, I, H, lin_amp(1.0, (double)H));
+                case 7: SPEC1(buf, I, 0.1, 0.0);
+                case 8: SPEC2(buf, H, I, lin_amp(1.0, (double)I));
+                case 4: case 10: SPEC1(buf, H, 0.2, 1.0);
+                default: SPEC1(buf, H, 0.1, 0.0);
+            }
+        }
+        return head_spec(c, i - GLC_BERT_TENSORS_FIXED - nl, name, shape, amp, mean);
     }
     if (c->backbone == GLC_BACKBONE_DECODER) {
         const uint64_t nqd = (uint64_t)c->heads * (uint64_t)c->head_dim;
@@ -317,19 +367,28 @@ static int load_blob(const char* path, glc_weights* w) {
     c->backbone = ints[17]; c->kv_heads = ints[18]; c->causal = ints[19];
     c->ln_eps = fl[0]; c->logit_scale = fl[1]; c->rope_theta = fl[2];
     c->qk_norm = 0; c->attn_bias = 1;         /* what every blob older than version 4 means */
-    if (ver == 3 || ver == 4) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
+    c->max_positions = 0; c->type_vocab = 0; c->pos_offset = 0;      /* ... and every blob older than version 5 */
+    if (ver >= 3 && ver <= 5) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
         int32_t i3[2];
         float f3;
         memcpy(i3, b + 16 + sizeof ints + sizeof fl, sizeof i3);
         memcpy(&f3, b + 16 + sizeof ints + sizeof fl + sizeof i3, sizeof f3);
         c->local_window = i3[0]; c->global_every = i3[1]; c->rope_theta_local = f3;
-        if (ver == 4) {      /* Llama / Qwen3 decoders: + qk_norm, attn_bias */
+        if (ver >= 4) {      /* Llama / Qwen3 decoders: + qk_norm, attn_bias */
             int32_t i4[2];
             memcpy(i4, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3, sizeof i4);
             c->qk_norm = i4[0]; c->attn_bias = i4[1];
+            if (ver == 5) {  /* written for the BERT backbone only: + max_positions, type_vocab, pos_offset */
+                int32_t i5[3];
+                memcpy(i5, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3 + sizeof i4, sizeof i5);
+                c->max_positions = i5[0]; c->type_vocab = i5[1]; c->pos_offset = i5[2];
+            }
         }
     }
-    if ((ver != 2 && ver != 3 && ver != 4) || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
+    const int bert_bad = (c->backbone == GLC_BACKBONE_BERT) != (ver == 5) ||
+                         (ver == 5 && (c->max_positions < 1 || c->max_positions > (1 << 24) || c->type_vocab < 1 || c->type_vocab > (1 << 16) ||
+                                       c->pos_offset < 0 || c->max_positions - c->pos_offset < 1));
+    if (ver < 2 || ver > 5 || bert_bad || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
         fprintf(stderr, "Error: '%s': unsupported GLCW header (version %u, %u tensors)\n", path, ver, nt);
         return -1;
     }

@@ -16,7 +16,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from .config import GLiClassConfig, BACKBONE_DECODER, BACKBONE_MODERNBERT, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
+from .config import GLiClassConfig, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
 from . import prng
 
 MAGIC = b"GLCW\x00\x01\x00\x00"
@@ -32,6 +32,8 @@ _V3_INT_FIELDS = ["local_window", "global_every"]
 _V3_F32_FIELDS = ["rope_theta_local"]
 # version 4 (decoder backbones other than Qwen2, i.e. (qk_norm, attn_bias) != (0, 1)): + qk_norm, attn_bias (int32) after the v3 slots
 _V4_INT_FIELDS = ["qk_norm", "attn_bias"]
+# version 5 (BERT backbone only): + max_positions, type_vocab, pos_offset (int32) after the v4 slots
+_V5_INT_FIELDS = ["max_positions", "type_vocab", "pos_offset"]
 
 
 def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float, float]]:
@@ -89,6 +91,35 @@ def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float,
                 (p + "mlp.Wo.weight", (H, I), lin(0.7, I), 0.0),
             ]
         specs += [("final_norm.weight", (H,), 0.2, 1.0)]
+        return specs + head_specs()
+
+    if cfg.backbone == BACKBONE_BERT:
+        # HF BertModel / RobertaModel / XLMRobertaModel.state_dict() names (prefix-free), with query / key / value fused into Wqkv (rows
+        # Q | K | V: from_state_dict and the C importer concatenate them).  The position and token-type rows are drawn smaller than the word
+        # rows and with a non-zero mean for the type rows, so that a dropped or mis-indexed row is visible in the output.
+        specs = [
+            ("embeddings.word_embeddings.weight", (cfg.vocab, H), 1.0, 0.0),
+            ("embeddings.position_embeddings.weight", (cfg.max_positions, H), 0.5, 0.0),
+            ("embeddings.token_type_embeddings.weight", (cfg.type_vocab, H), 0.3, 0.1),
+            ("embeddings.LayerNorm.weight", (H,), 0.2, 1.0),
+            ("embeddings.LayerNorm.bias", (H,), 0.1, 0.0),
+        ]
+        for i in range(L):
+            p = f"encoder.layer.{i}."
+            specs += [
+                (p + "attention.self.Wqkv.weight", (3 * H, H), lin(1.6, H), 0.0),
+                (p + "attention.self.Wqkv.bias", (3 * H,), 0.1, 0.0),
+                (p + "attention.output.dense.weight", (H, H), lin(1.0, H), 0.0),
+                (p + "attention.output.dense.bias", (H,), 0.1, 0.0),
+                (p + "attention.output.LayerNorm.weight", (H,), 0.2, 1.0),
+                (p + "attention.output.LayerNorm.bias", (H,), 0.1, 0.0),
+                (p + "intermediate.dense.weight", (I, H), lin(1.0, H), 0.0),
+                (p + "intermediate.dense.bias", (I,), 0.1, 0.0),
+                (p + "output.dense.weight", (H, I), lin(1.0, I), 0.0),
+                (p + "output.dense.bias", (H,), 0.1, 0.0),
+                (p + "output.LayerNorm.weight", (H,), 0.2, 1.0),
+                (p + "output.LayerNorm.bias", (H,), 0.1, 0.0),
+            ]
         return specs + head_specs()
 
     if cfg.backbone == BACKBONE_DECODER:
@@ -157,9 +188,10 @@ def make_weights(cfg: GLiClassConfig, seed: int = 42) -> Dict[str, np.ndarray]:
 
 def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
     d = cfg.asdict()
-    v4 = (cfg.qk_norm, cfg.attn_bias) != (0, 1)       # Llama / Qwen3 decoders; v4 carries the v3 slots too
+    v5 = cfg.backbone == BACKBONE_BERT                # v5 carries the v3 and v4 slots too
+    v4 = v5 or (cfg.qk_norm, cfg.attn_bias) != (0, 1)       # Llama / Qwen3 decoders; v4 carries the v3 slots too
     v3 = cfg.backbone == BACKBONE_MODERNBERT          # every other backbone keeps writing byte-identical v2 headers
-    b = MAGIC + struct.pack("<II", 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
+    b = MAGIC + struct.pack("<II", 5 if v5 else 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
     b += struct.pack("<%di" % len(_INT_FIELDS), *[int(d[k]) for k in _INT_FIELDS])
     b += struct.pack("<%df" % len(_F32_FIELDS), *[float(d[k]) for k in _F32_FIELDS])
     if v3 or v4:
@@ -167,6 +199,8 @@ def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
         b += struct.pack("<%df" % len(_V3_F32_FIELDS), *[float(d[k]) for k in _V3_F32_FIELDS])
     if v4:
         b += struct.pack("<%di" % len(_V4_INT_FIELDS), *[int(d[k]) for k in _V4_INT_FIELDS])
+    if v5:
+        b += struct.pack("<%di" % len(_V5_INT_FIELDS), *[int(d[k]) for k in _V5_INT_FIELDS])
     assert len(b) <= HEADER_BYTES
     return b + b"\x00" * (HEADER_BYTES - len(b))
 
@@ -204,7 +238,7 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if hdr[:8] != MAGIC:
         raise ValueError("not a GLCW blob")
     ver, n_t = struct.unpack_from("<II", hdr, 8)
-    if ver not in (2, 3, 4):
+    if ver not in (2, 3, 4, 5):
         raise ValueError(f"unsupported GLCW version {ver}")
     ints = struct.unpack_from("<%di" % len(_INT_FIELDS), hdr, 16)
     flts = struct.unpack_from("<%df" % len(_F32_FIELDS), hdr, 16 + 4 * len(_INT_FIELDS))
@@ -217,6 +251,9 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if ver >= 4:          # older blobs mean (qk_norm, attn_bias) = (0, 1), the dataclass defaults
         o4 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS))
         kw.update(dict(zip(_V4_INT_FIELDS, struct.unpack_from("<%di" % len(_V4_INT_FIELDS), hdr, o4))))
+    if ver >= 5:
+        o5 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS) + len(_V4_INT_FIELDS))
+        kw.update(dict(zip(_V5_INT_FIELDS, struct.unpack_from("<%di" % len(_V5_INT_FIELDS), hdr, o5))))
     cfg = GLiClassConfig(name="blob", **kw)
     tensors = {}
     for i in range(n_t):
@@ -228,19 +265,87 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     return cfg, tensors
 
 
-def from_state_dict(sd: Dict[str, "np.ndarray"], cfg: GLiClassConfig) -> Dict[str, np.ndarray]:
-    """Rename a (GLiClass or bare DebertaV2Model) state_dict to blob names.
+def from_state_dict(sd: Dict[str, "np.ndarray"], cfg: GLiClassConfig, names=None) -> Dict[str, np.ndarray]:
+    """Rename a (GLiClass or bare backbone) state_dict to blob names.
 
-    Accepts the prefixes HF / gliclass checkpoints use (`deberta.`, `encoder_model.model.`, none).
+    Accepts the prefixes HF / gliclass checkpoints use (`deberta.`, `encoder_model.model.`, none).  `names`: the blob names to
+    convert (default: every tensor of the config; a bare backbone has no head tensors).
     """
     out = {}
-    want = [s[0] for s in tensor_specs(cfg)]
-    for n in want:
-        for pre in ("", "deberta.", "encoder_model.model.", "model.encoder_model.model.", "model.", "decoder_model.model."):
+    want = [s[0] for s in tensor_specs(cfg)] if names is None else list(names)
+    prefixes = ("", "deberta.", "encoder_model.model.", "model.encoder_model.model.", "model.", "decoder_model.model.") + \
+        (_BERT_PREFIXES if cfg.backbone == BACKBONE_BERT else ())
+
+    def find(n):
+        for pre in prefixes:
             if pre + n in sd:
                 v = sd[pre + n]
-                out[n] = v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32)
-                break
+                return v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32)
+        raise KeyError(n)
+
+    for n in want:
+        if cfg.backbone == BACKBONE_BERT and ".attention.self.Wqkv." in n:      # HF keeps query / key / value apart: rows Q | K | V
+            out[n] = np.concatenate([find(n.replace("Wqkv", part)) for part in ("query", "key", "value")], axis=0)
         else:
-            raise KeyError(n)
+            out[n] = find(n)
     return out
+
+
+# ---- BERT / RoBERTa / XLM-R checkpoints (mirrors parse_config of host/glc_safetensors.c) ----
+BERT_MODEL_TYPES = ("bert", "roberta", "xlm-roberta")
+_BERT_PREFIXES = ("bert.", "roberta.", "encoder_model.", "model.encoder_model.", "encoder_model.bert.", "encoder_model.roberta.",
+                  "model.encoder_model.bert.", "model.encoder_model.roberta.")
+
+
+def bert_config_from_hf(root: dict, vocab: int = None) -> GLiClassConfig:
+    """GLiClassConfig of a BERT-family checkpoint's config.json (`root`; the backbone's own fields under encoder_config, or a bare
+    backbone config).  `vocab` = rows of the word-embedding matrix (tokens were added after the backbone config was written).
+    Everything the engine does not build is refused with a message that names the field."""
+    from .config import SCORER_NAMES, POOL_FIRST, POOL_AVG, POOL_LAST
+    enc = root.get("encoder_config") if isinstance(root.get("encoder_config"), dict) else root
+    mt = enc.get("model_type")
+    if mt not in BERT_MODEL_TYPES:
+        raise ValueError(f"backbone model_type '{mt}' is not a BERT-family type (bert, roberta, xlm-roberta)")
+    pet = enc.get("position_embedding_type", "absolute")
+    if pet != "absolute":
+        raise ValueError(f"position_embedding_type '{pet}' is not implemented (absolute)")
+    act = enc.get("hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"hidden_act '{act}' is not implemented (gelu)")
+    if enc.get("is_decoder", False):
+        raise ValueError("is_decoder=true is not implemented")
+    if enc.get("add_cross_attention", False):
+        raise ValueError("add_cross_attention=true is not implemented")
+    H, nh = int(enc["hidden_size"]), int(enc["num_attention_heads"])
+    if H % nh or H // nh != 64:
+        raise ValueError(f"head_dim {H // nh} is not implemented (64)")
+    pad = int(enc.get("pad_token_id", 0 if mt == "bert" else 1))
+    off = 0 if mt == "bert" else pad + 1
+    P = int(enc.get("max_position_embeddings", 512))
+    if P - off < 1:
+        raise ValueError(f"max_position_embeddings {P} leaves no position behind the offset {off}")
+    pool = {"first": POOL_FIRST, "avg": POOL_AVG, "last": POOL_LAST}[root.get("pooling_strategy", "first")]
+    vocab = int(vocab if vocab is not None else root.get("vocab_size", enc.get("vocab_size")))
+    return GLiClassConfig(
+        name="checkpoint", vocab=vocab, hidden=H, layers=int(enc["num_hidden_layers"]), heads=nh, inter=int(enc["intermediate_size"]),
+        pos_buckets=0, max_rel_pos=0, ln_eps=float(enc.get("layer_norm_eps", 1e-12)), pad_id=pad,
+        cls_id=int(enc.get("cls_token_id", enc.get("bos_token_id", 1))), sep_id=int(enc.get("sep_token_id", enc.get("eos_token_id", 2))),
+        class_token_index=int(root.get("class_token_index", -1)), text_token_index=int(root.get("text_token_index", -1)), pooling=pool,
+        scorer=SCORER_NAMES[root.get("scorer_type", "simple")], embed_class_token=int(bool(root.get("embed_class_token", True))),
+        normalize_features=int(bool(root.get("normalize_features", False))), logit_scale=float(root.get("logit_scale", 1.0)),
+        backbone=BACKBONE_BERT, causal=0, max_positions=P, type_vocab=int(enc.get("type_vocab_size", 2)), pos_offset=off)
+
+
+def load_bert_checkpoint(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
+    """An HF directory (config.json + model.safetensors) of a BERT-family backbone -> (config, tensors in blob order)."""
+    import json
+    import os
+    from safetensors.numpy import load_file
+    with open(os.path.join(path, "config.json")) as f:
+        root = json.load(f)
+    sd = load_file(os.path.join(path, "model.safetensors"))
+    emb = [v for k, v in sd.items() if k.endswith("embeddings.word_embeddings.weight")]
+    if not emb:
+        raise KeyError("embeddings.word_embeddings.weight")
+    cfg = bert_config_from_hf(root, vocab=emb[0].shape[0])
+    return cfg, from_state_dict(sd, cfg)

@@ -39,7 +39,10 @@ enum { GLC_SCORER_DOT = 0, GLC_SCORER_WEIGHTED_DOT = 1, GLC_SCORER_MLP = 2 };
  * grouped-query attention, SwiGLU; SURVEY.md §8a row a16, BASELINE.json configs[4]; glc_model_config qk_norm / attn_bias tell the three apart) */
 enum { GLC_BACKBONE_DEBERTA = 0, GLC_BACKBONE_DECODER = 1,
        GLC_BACKBONE_MODERNBERT = 2 /* ModernBERT encoder: LayerNorm without bias, RoPE, bidirectional attention with a sliding window on the
-                                      local layers, GeGLU (transformers models/modernbert/modeling_modernbert.py) */ };
+                                      local layers, GeGLU (transformers models/modernbert/modeling_modernbert.py) */,
+       GLC_BACKBONE_BERT = 3 /* BERT / RoBERTa / XLM-R encoder: learned absolute position embeddings (+ token-type row 0), post-LayerNorm blocks
+                                with biases, plain bidirectional attention, erf-GELU FFN (transformers models/bert/modeling_bert.py,
+                                models/roberta/modeling_roberta.py) */ };
 
 /* Same int/float slots, same order, as the .glcw blob header (gliclass/c_amd/weights.py). */
 typedef struct glc_model_config {
@@ -56,6 +59,10 @@ typedef struct glc_model_config {
     /* decoder backbone: qk_norm = 1 applies an RMSNorm over head_dim (gains q_norm / k_norm, epsilon ln_eps) to every query and key head
      * before RoPE (Qwen3); attn_bias = 0 drops the q / k / v projection biases (Llama, Qwen3).  Qwen2 is (0, 1), and so is every other backbone. */
     int32_t qk_norm, attn_bias;
+    /* BERT backbone: rows of the position table (max_position_embeddings) and of the token-type table; pos_offset = 0 numbers the positions
+     * 0 .. S-1 (BERT), pos_offset = pad_id + 1 numbers the non-pad tokens from pos_offset on and gives pad tokens row pad_id (RoBERTa / XLM-R,
+     * create_position_ids_from_input_ids).  A forward takes at most max_positions - pos_offset tokens per row.  0 on every other backbone. */
+    int32_t max_positions, type_vocab, pos_offset;
 } glc_model_config;
 
 /* Tensor order expected in `tensors[]` (all fp32, row-major, nn.Linear weights are [out,in]):
@@ -90,7 +97,18 @@ static inline int glc_dec_tensors_per_layer(const glc_model_config* c) { return 
  *                     mlp_norm.weight [H]  mlp.Wi.weight [2I,H] (rows: input | gate)  mlp.Wo.weight [H,I]
  *   then final_norm.weight [H], then the same 8 head tensors */
 #define GLC_MB_TENSORS_PER_LAYER 6
+/* BERT backbone (names of HF BertModel / RobertaModel / XLMRobertaModel.state_dict() except the fused attention projection; the pooler is ignored):
+ *   0 embeddings.word_embeddings.weight [vocab,H]      1 embeddings.position_embeddings.weight [max_positions,H]
+ *   2 embeddings.token_type_embeddings.weight [type_vocab,H]      3,4 embeddings.LayerNorm.{weight,bias}
+ *   5+12*l .. : layer l: attention.self.Wqkv.weight [3H,H] (rows: query | key | value, concatenated by the importers)  attention.self.Wqkv.bias [3H]
+ *                        attention.output.dense.{weight,bias}  attention.output.LayerNorm.{weight,bias}
+ *                        intermediate.dense.{weight [I,H],bias}  output.dense.{weight [H,I],bias}  output.LayerNorm.{weight,bias}
+ *   then the same 8 head tensors */
+#define GLC_BERT_TENSORS_FIXED 5
+#define GLC_BERT_TENSORS_PER_LAYER 12
 static inline int glc_num_tensors_cfg(const glc_model_config* c) {
+    if (c->backbone == GLC_BACKBONE_BERT)
+        return GLC_BERT_TENSORS_FIXED + GLC_BERT_TENSORS_PER_LAYER * c->layers + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     if (c->backbone == GLC_BACKBONE_MODERNBERT)
         return 3 + GLC_MB_TENSORS_PER_LAYER * c->layers - (c->layers > 0 ? 1 : 0) + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     return (c->backbone == GLC_BACKBONE_DECODER ? 2 + glc_dec_tensors_per_layer(c) * c->layers + GLC_TENSORS_HEAD : glc_num_tensors(c->layers)) +
@@ -145,7 +163,8 @@ int glc_engine_device_forward_valid(glc_engine* e);      /* 1 valid / 0 repeat t
  * inter % 32 == 0 (modernbert-large, 2 x 2624 = 5248, is not eligible); head_dim 64; not under glc_debug_keep_hidden.  The activation
  * exponent is chosen here from the LayerNorm gains (max |gamma| sqrt(hidden) > 448: exponent -5 from the start).  Afterwards GLICLASS_MX=build,
  * glc_debug_set_mx, glc_debug_set_mx_attention, the glc_debug_last_forward_mx* queries and the fp8 range guard behave as on the decoder
- * backbone.  On the other backbones: 0 if the MX pipeline is available to the engine, else -1; nothing changes.
+ * backbone.  On the other backbones: 0 if the MX pipeline is available to the engine, else -1; nothing changes (the BERT backbone has no MX
+ * pipeline: always -1, the message says so).
  * Environment: GLICLASS_MX_MODERNBERT=1, read once in glc_engine_create, makes this call for a ModernBERT engine (a failure leaves the
  * engine as it is and is not an error). */
 int glc_engine_enable_mx(glc_engine* e);
@@ -185,7 +204,7 @@ int glc_debug_graph_cache_size(const glc_engine* e);       /* graph executables 
  * arithmetic's ~4e-5 — the error large forwards have by default; that is why it is opt-in.  The fp8 range guard, its retries and
  * glc_engine_sync's report apply unchanged.  Speed: not measured yet; nothing is promised.
  * Changing the mode drops every cached graph.  Returns 0; -1 (glc_last_error) for a null engine, a mode outside 0 .. 2, or mode >= 1 on the
- * decoder / ModernBERT backbones (the message names the backbone; mode 0 returns 0 there).
+ * decoder / ModernBERT / BERT backbones (the message names the backbone; mode 0 returns 0 there).
  * Environment: GLICLASS_MX_SMALL=1|2, read once in glc_engine_create, makes this call (a failure leaves the engine as it is, not an error). */
 int glc_engine_set_mx_small_forwards(glc_engine* e, int mode);
 int glc_debug_last_forward_mx128(const glc_engine* e);     /* GEMM launches of the last forward that ran on the 128 tile (0: none); -1: null engine */
@@ -193,7 +212,9 @@ int glc_debug_last_forward_mx128(const glc_engine* e);     /* GEMM launches of t
 /* Exact last-layer pruning (default on; env GLICLASS_PRUNE_LAST=0 disables), on every backbone: the final layer computes attention
  * output, output projection and FFN (DeBERTa: Q as well) only for the rows the head reads — the pooled row of each sequence ([CLS] /
  * position 0, or the last attended token with 'last' pooling) and its class tokens; K and V are still made for every position.  Logits
- * are unchanged.  Never with average pooling (it reads every row) and never under glc_debug_keep_hidden (it dumps every row). */
+ * are unchanged.  Never with average pooling (it reads every row) and never under glc_debug_keep_hidden (it dumps every row).
+ * Not on the BERT backbone: its last layer runs on every row and glc_debug_last_forward_pruned answers 0 (post-LayerNorm pruning on the
+ * compact path is a follow-up); the switch is accepted and has no effect there. */
 int glc_engine_set_prune_last_layer(glc_engine* e, int on);
 int glc_debug_last_forward_pruned(const glc_engine* e);        /* 1: the last forward ran that compact last layer, 0: it did not, -1: null engine */
 
@@ -247,6 +268,8 @@ long long glc_debug_mx_weight_bytes(const glc_engine* e);  /* bytes of the GX we
 /* Developer: stop forwards after a stage (engine.hip) and read workspace rows decoded to fp32 (engine_debug.hip). */
 int glc_debug_set_stop(glc_engine* e, int stage);
 int glc_debug_read_workspace(glc_engine* e, int which, int rows, float* out);
+/* BERT backbone: the position ids [B, Sp] (Sp = S rounded up to 64) of the last forward, as the embedding kernel read them; n = B * Sp */
+int glc_debug_read_pos_ids(glc_engine* e, int32_t* out, int n);
 /* Group-split pipeline: LayerNorm folded into the GEMMs around it (1, default: the producer writes raw rows + row statistics, the consumer
  * runs on weights with gamma folded in and finishes (LN(x) W^T + b) in its epilogue) or as kernels of its own (0). */
 int glc_debug_set_ln_fused(glc_engine* e, int on);
