@@ -15,7 +15,7 @@ SCORER_WEIGHTED_DOT = 1
 SCORER_MLP = 2
 SCORER_MLP_HIDDEN = 256
 SCORER_NAMES = {"simple": SCORER_DOT, "weighted-dot": SCORER_WEIGHTED_DOT, "mlp": SCORER_MLP}
-BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT = 0, 1, 2, 3
+BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, BACKBONE_T5 = 0, 1, 2, 3, 4
 
 
 @dataclass(frozen=True)
@@ -62,10 +62,15 @@ class GLiClassConfig:
     max_positions: int = 0
     type_vocab: int = 0
     pos_offset: int = 0
+    # T5 backbone (transformers models/t5, the encoder stack): relative_attention_num_buckets / relative_attention_max_distance of the
+    # learned bias table [rel_buckets, heads] (layer 0's, shared by all layers); head_dim is d_kv = 64, heads * head_dim need not be
+    # `hidden` (mt5-small: 6 x 64 on 512); ln_eps is layer_norm_epsilon, `inter` d_ff (the gated-gelu width)
+    rel_buckets: int = 0
+    rel_max_distance: int = 0
 
     def __post_init__(self):
-        # (a decoder checkpoint names its head_dim: Qwen3's is not hidden / heads)
-        assert self.backbone == BACKBONE_DECODER or self.hidden == self.heads * self.head_dim
+        # (a decoder checkpoint names its head_dim: Qwen3's is not hidden / heads; T5's inner width is num_heads * d_kv)
+        assert self.backbone in (BACKBONE_DECODER, BACKBONE_T5) or self.hidden == self.heads * self.head_dim
         assert self.qk_norm in (0, 1) and self.attn_bias in (0, 1) and (self.backbone == BACKBONE_DECODER or self.qk_norm == 0)
         if self.kv_heads <= 0:
             object.__setattr__(self, "kv_heads", self.heads)
@@ -73,6 +78,8 @@ class GLiClassConfig:
         if self.backbone == BACKBONE_BERT:
             assert self.head_dim == 64 and self.type_vocab >= 1 and self.pos_offset in (0, self.pad_id + 1)
             assert self.max_positions - self.pos_offset >= 1
+        if self.backbone == BACKBONE_T5:
+            assert self.head_dim == 64 and self.rel_buckets >= 4 and self.rel_buckets % 4 == 0 and self.rel_max_distance > self.rel_buckets // 4
         if self.class_token_index < 0:
             object.__setattr__(self, "class_token_index", self.vocab - 2)
         if self.text_token_index < 0:
@@ -89,6 +96,9 @@ class GLiClassConfig:
         H, I, L, P = self.hidden, self.inter, self.layers, 2 * self.att_span
         if self.backbone == BACKBONE_BERT:          # the DeBERTa count without its position projections
             return L * S * (8 * H * H + 4 * H * I + 4 * S * H) + 8 * H * H * (1 + C)
+        if self.backbone == BACKBONE_T5:            # the decoder count with nq = nkv = heads and full (bidirectional) attention
+            nqd = self.heads * self.head_dim
+            return L * S * (8 * H * nqd + 6 * H * I + 4 * S * nqd) + 8 * H * H * (1 + C)
         if self.backbone == BACKBONE_MODERNBERT:
             keys = sum(S if self.is_global_layer(l) else min(S, 2 * self.local_window + 1) for l in range(L))
             return L * S * (8 * H * H + 6 * H * I) + 4 * S * H * keys + 8 * H * H * (1 + C)
@@ -152,4 +162,15 @@ CONFIGS = {
                                 backbone=BACKBONE_BERT, causal=0, max_positions=2050, type_vocab=1, pos_offset=2),
     "bert-base": GLiClassConfig("bert-base", vocab=30522, hidden=768, layers=12, heads=12, inter=3072, ln_eps=1e-12, pad_id=0, cls_id=101,
                                 sep_id=102, backbone=BACKBONE_BERT, causal=0, max_positions=512, type_vocab=2, pos_offset=0),
+    # T5 v1.1 / mT5 backbones (gated-gelu, 32 buckets up to distance 128): t5-tiny (H % 256 != 0: the plain paths), t5-odd (3 heads: inner
+    # width 192 != hidden, and an odd head count) and t5-mini (group-split eligible) are the parity configs, t5-base the published
+    # T5 v1.1 base shape (vocab 32 128)
+    "t5-tiny": GLiClassConfig("t5-tiny", vocab=515, hidden=128, layers=2, heads=2, inter=256, ln_eps=1e-6, backbone=BACKBONE_T5, causal=0,
+                              pos_buckets=0, max_rel_pos=0, rel_buckets=32, rel_max_distance=128),
+    "t5-odd": GLiClassConfig("t5-odd", vocab=515, hidden=128, layers=2, heads=3, inter=256, ln_eps=1e-6, backbone=BACKBONE_T5, causal=0,
+                             pos_buckets=0, max_rel_pos=0, rel_buckets=32, rel_max_distance=128),
+    "t5-mini": GLiClassConfig("t5-mini", vocab=1027, hidden=256, layers=3, heads=4, inter=512, ln_eps=1e-6, backbone=BACKBONE_T5, causal=0,
+                              pos_buckets=0, max_rel_pos=0, rel_buckets=32, rel_max_distance=128),
+    "t5-base": GLiClassConfig("t5-base", vocab=32128, hidden=768, layers=12, heads=12, inter=2048, ln_eps=1e-6, backbone=BACKBONE_T5, causal=0,
+                              pos_buckets=0, max_rel_pos=0, rel_buckets=32, rel_max_distance=128),
 }

@@ -11,6 +11,8 @@
 //   attn_gqa      Q2:160-170  grouped-query attention with causal and key-padding mask (create_causal_mask), exp2 softmax; with a
 //                 window W (ModernBERT's local layers, modeling_modernbert.py) keys with |q - k| > W are masked and never visited
 //   geglu         ModernBERT MLP: gelu(input) * gate on the fused [input | gate] projection (the SwiGLU kernels with the erf GELU)
+//   geglu_tanh    T5 v1.1 / mT5 (models/t5/modeling_t5.py T5DenseGatedActDense): gelu_new(wi_0 x) * wi_1 x, the same kernels with the tanh GELU
+//   rpb           T5Attention.compute_bias: both attention kernels add a per-head bias indexed by key - query (template flag RPB)
 // Row kernels are HBM streams: one wave per row, 16-byte vectors.
 #include "glc_common.h"
 #include "glc_kernels.h"
@@ -93,9 +95,18 @@ __global__ __launch_bounds__(256) void rmsnorm_gs_kernel(const float* __restrict
         gs_store8(y, ch * 8, o);
     }
 }
+// gelu_new (transformers activations.py NewGELUActivation, T5 v1.1's dense_act_fn): 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) =
+// x sigmoid(2 u) = x / (1 + exp(-2 u)), u the tanh's argument: no cancellation at either tail (exp overflows to inf for x << 0: x / inf = -0)
+__device__ __forceinline__ float gelu_tanh_f32(float x) {
+    const float u2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);      // 2 sqrt(2/pi) (x + 0.044715 x^3)
+    return x * __builtin_amdgcn_rcpf(1.0f + __expf(-u2));
+}
+enum { GLU_SILU = 0, GLU_GELU = 1, GLU_GELU_TANH = 2 };
+
 // F[m, i] = silu(GU[m, i]) * GU[m, I + i]: plain fp32 [gate | up] rows in, group-split rows out
-// (GELU: gelu(GU[m, i]) * GU[m, I + i], ModernBERT's GeGLU on [input | gate], erf GELU at fp32 resolution as the EPI_GELU epilogue)
-template <bool GELU>
+// (GLU_GELU: gelu(GU[m, i]) * GU[m, I + i], ModernBERT's GeGLU on [input | gate], erf GELU at fp32 resolution as the EPI_GELU epilogue;
+//  GLU_GELU_TANH: the same with gelu_new, T5's gated-gelu on [wi_0 | wi_1])
+template <int ACT>
 __global__ __launch_bounds__(256) void swiglu_gs_kernel(const float* __restrict__ GU, f16_t* __restrict__ F, size_t M, int I) {
     const size_t nch = (size_t)I / 8, total = M * nch;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -104,12 +115,15 @@ __global__ __launch_bounds__(256) void swiglu_gs_kernel(const float* __restrict_
         const f32x4 g0 = *reinterpret_cast<const f32x4*>(g), g1 = *reinterpret_cast<const f32x4*>(g + 4);
         const f32x4 u0 = *reinterpret_cast<const f32x4*>(g + I), u1 = *reinterpret_cast<const f32x4*>(g + I + 4);
         float o[8];
-        if constexpr (GELU) {
+        if constexpr (ACT == GLU_GELU) {
 #pragma unroll
             for (int e = 0; e < 4; e += 2) {
                 const f32x2 a = glc_gelu2_f32((f32x2){g0[e], g0[e + 1]}), b = glc_gelu2_f32((f32x2){g1[e], g1[e + 1]});
                 o[e] = a[0] * u0[e]; o[e + 1] = a[1] * u0[e + 1]; o[4 + e] = b[0] * u1[e]; o[5 + e] = b[1] * u1[e + 1];
             }
+        } else if constexpr (ACT == GLU_GELU_TANH) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { o[e] = gelu_tanh_f32(g0[e]) * u0[e]; o[4 + e] = gelu_tanh_f32(g1[e]) * u1[e]; }
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -158,7 +172,7 @@ __global__ __launch_bounds__(256) void rope_qk_kernel(T* __restrict__ QKV, const
 // F[m, i] = silu(GU[m, i]) * GU[m, I + i]   (GELU: gelu(GU[m, i]) * GU[m, I + i], ModernBERT's GeGLU, erf GELU in fp32)
 // inter = 1: the [gate | up] columns interleave 16 gate / 16 up features (the fused weight layout of the SwiGLU GEMM epilogue,
 // engine.hip): feature i's gate is column 32 (i / 16) + i % 16, its up column 16 further on
-template <typename T, bool GELU = false>
+template <typename T, int ACT = GLU_SILU>
 __global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ GU, T* __restrict__ F, size_t M, int I, int inter) {
     typedef typename Vec16<T>::type vecT;
     constexpr int VEC = Vec16<T>::N;
@@ -170,12 +184,15 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ GU, T
         const vecT g = *reinterpret_cast<const vecT*>(GU + m * 2 * I + gcol);
         const vecT u = *reinterpret_cast<const vecT*>(GU + m * 2 * I + ucol);
         vecT o;
-        if constexpr (GELU) {
+        if constexpr (ACT == GLU_GELU) {
 #pragma unroll
             for (int e = 0; e < VEC; e += 2) {
                 const f32x2 a = glc_gelu2_f32((f32x2){(float)g[e], (float)g[e + 1]});
                 o[e] = (T)(a[0] * (float)u[e]); o[e + 1] = (T)(a[1] * (float)u[e + 1]);
             }
+        } else if constexpr (ACT == GLU_GELU_TANH) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) o[e] = (T)(gelu_tanh_f32((float)g[e]) * (float)u[e]);
         } else {
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
@@ -190,10 +207,12 @@ __global__ __launch_bounds__(256) void swiglu_kernel(const T* __restrict__ GU, T
 // Straightforward grouped-query attention (any T, no MFMA): one block per (query row, head).  Q already carries
 // log2(e)/sqrt(d); scores are in log2 units.  Keys j > q are excluded when causal; padded keys carry the -1e30 bias.
 // window > 0: only keys q - window .. q + window are visited (ModernBERT's local layers).
-template <typename T>
+// RPB (T5, modeling_t5.py T5Attention.compute_bias): rpb [nq][2 Sp] holds the head's relative-position bias in log2 units, entry
+// (k - q) + Sp - 1; it is added to the score before the key mask.  RPB = false never reads the pointer.
+template <typename T, bool RPB = false>
 __global__ __launch_bounds__(256) void attn_gqa_simple_kernel(const T* __restrict__ QKV, const float* __restrict__ kbias,
                                                               const int* __restrict__ klen, T* __restrict__ CTX, int Sp, int nq, int nkv,
-                                                              int d, int causal, int window) {
+                                                              int d, int causal, int window, const float* __restrict__ rpb = nullptr) {
     typedef typename Vec16<T>::type vecT;
     constexpr int VEC = Vec16<T>::N;
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -227,6 +246,7 @@ __global__ __launch_bounds__(256) void attn_gqa_simple_kernel(const T* __restric
 #pragma unroll
             for (int e = 0; e < VEC; ++e) s += qv[e0 + e] * (float)kv[e];
         }
+        if constexpr (RPB) s += rpb[(size_t)h * 2 * Sp + (k - q + Sp - 1)];
         s += kb[k];
         sc[k] = s;
         mx = fmaxf(mx, s);
@@ -288,15 +308,16 @@ const char* glc_launch_rmsnorm_gs(hipStream_t st, const float* X, void* Y, const
     hipLaunchKernelGGL(rmsnorm_gs_kernel, dim3((M + 3) / 4), dim3(256), 0, st, X, (f16_t*)Y, w, eps, M, H);
     return nullptr;
 }
-template <bool GELU> static const char* launch_glu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) {
-    if (!GU || !F || M == 0 || I <= 0 || I % 32) return GELU ? "geglu_gs: bad args" : "swiglu_gs: bad args";
+template <int ACT> static const char* launch_glu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) {
+    if (!GU || !F || M == 0 || I <= 0 || I % 32) return ACT == GLU_GELU_TANH ? "geglu_tanh_gs: bad args" : ACT == GLU_GELU ? "geglu_gs: bad args" : "swiglu_gs: bad args";
     const size_t total = M * ((size_t)I / 8);
     const unsigned grid = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    hipLaunchKernelGGL(swiglu_gs_kernel<GELU>, dim3(grid), dim3(256), 0, st, GU, (f16_t*)F, M, I);
+    hipLaunchKernelGGL(swiglu_gs_kernel<ACT>, dim3(grid), dim3(256), 0, st, GU, (f16_t*)F, M, I);
     return nullptr;
 }
-const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<false>(st, GU, F, M, I); }
-const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<true>(st, GU, F, M, I); }
+const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<GLU_SILU>(st, GU, F, M, I); }
+const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<GLU_GELU>(st, GU, F, M, I); }
+const char* glc_launch_geglu_tanh_gs(hipStream_t st, const float* GU, void* F, size_t M, int I) { return launch_glu_gs<GLU_GELU_TANH>(st, GU, F, M, I); }
 
 const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float* cs, int M, int Sp, int nq, int nkv, int d, float qscale,
                                const float* qn, const float* kn, float eps) {
@@ -311,30 +332,34 @@ const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float
     return nullptr;
 }
 
-template <bool GELU> static const char* launch_glu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) {
-    if (M == 0 || I <= 0 || I % 8 || (inter && I % 16) || !GU || !F) return GELU ? "geglu: bad args" : "swiglu: bad args";
+template <int ACT> static const char* launch_glu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) {
+    if (M == 0 || I <= 0 || I % 8 || (inter && I % 16) || !GU || !F) return ACT == GLU_GELU_TANH ? "geglu_tanh: bad args" : ACT == GLU_GELU ? "geglu: bad args" : "swiglu: bad args";
     DISPATCH_T(dtype, {
         const size_t total = M * ((size_t)I / Vec16<T>::N);
         size_t blocks = (total + 255) / 256;
         if (blocks > 256 * 64) blocks = 256 * 64;
-        hipLaunchKernelGGL((swiglu_kernel<T, GELU>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)GU, (T*)F, M, I, inter);
+        hipLaunchKernelGGL((swiglu_kernel<T, ACT>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)GU, (T*)F, M, I, inter);
     });
     return nullptr;
 }
-const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<false>(st, dtype, GU, F, M, I, inter); }
-const char* glc_launch_geglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<true>(st, dtype, GU, F, M, I, inter); }
+const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<GLU_SILU>(st, dtype, GU, F, M, I, inter); }
+const char* glc_launch_geglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<GLU_GELU>(st, dtype, GU, F, M, I, inter); }
+const char* glc_launch_geglu_tanh(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter) { return launch_glu<GLU_GELU_TANH>(st, dtype, GU, F, M, I, inter); }
 
 // impl: 1 = straightforward kernel (any T)
 const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const void* QKV, const float* kbias, const int* klen, void* CTX,
-                                     int B, int Sp, int nq, int nkv, int d, int causal, int window) {
+                                     int B, int Sp, int nq, int nkv, int d, int causal, int window, const float* rpb) {
     if (!QKV || !kbias || !klen || !CTX || B <= 0 || Sp <= 0 || nq <= 0 || nkv <= 0 || nq % nkv || window < 0) return "attention_gqa: bad args";
+    if (rpb && (causal || window > 0)) return "attention_gqa: the relative-position bias takes no causal mask and no window";
     if (d != 64 && d != 128) return "attention_gqa: head_dim must be 64 or 128";
     if (impl != 1) return "attention_gqa: unknown implementation";
     const size_t shm = (size_t)(d + 256 + Sp) * sizeof(float);
     if (shm > 64 * 1024) return "attention_gqa(simple): sequence too long for the straightforward kernel";
     DISPATCH_T(dtype, {
-        hipLaunchKernelGGL(attn_gqa_simple_kernel<T>, dim3(Sp, nq, B), dim3(256), shm, st, (const T*)QKV, kbias, klen, (T*)CTX, Sp, nq, nkv, d,
-                           causal, window);
+        if (rpb) hipLaunchKernelGGL((attn_gqa_simple_kernel<T, true>), dim3(Sp, nq, B), dim3(256), shm, st, (const T*)QKV, kbias, klen, (T*)CTX, Sp, nq, nkv, d,
+                                    causal, window, rpb);
+        else hipLaunchKernelGGL(attn_gqa_simple_kernel<T>, dim3(Sp, nq, B), dim3(256), shm, st, (const T*)QKV, kbias, klen, (T*)CTX, Sp, nq, nkv, d,
+                                causal, window, nullptr);
     });
     return nullptr;
 }
@@ -464,13 +489,21 @@ template <typename T> struct GqaFrag<true, T> { typedef f16x8s type; };
 // WIN: sliding window of half-width `win` (keys with |q - k| > win masked), see above; WIN = false ignores `win`.
 // tile_flag (pruned last layer, engine.hip): one byte per 32-query tile [B, Sp / 32]; a wave whose tile is unflagged returns at once — no
 // load, no store: nobody reads its context rows.  Null = every tile, as before: a wave-uniform branch on the pointer, not a template parameter.
-template <typename T, int D, bool SPLIT = false, bool WIN = false>
+// RPB (T5's relative-position bias, modeling_t5.py T5Attention.compute_bias; D = 64, no window, causal = 0 from the caller): rpb [nq][2 Sp]
+// fp32 holds rel_bias[bucket(delta), head] log2(e) at entry delta + Sp - 1, delta = key - query (engine.hip build_rpb_table).  Lane (query c)
+// adds entries (k0 + ko) - (q0 + c) + Sp - 1 to its 16 scores: two runs of eight consecutive floats, at an address that moves with c, so
+// they are 16 dword loads through L1 (a head's whole table is 8 Sp bytes and a key tile touches 63 entries of it: 252 B, L1-resident
+// after the first wave).  They are issued ahead of the S^T MFMAs, which hide them; no LDS, so the kernel keeps its barrier-free
+// early returns.  The bias goes in before the key mask and the running maximum.
+template <typename T, int D, bool SPLIT = false, bool WIN = false, bool RPB = false>
 __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const T* __restrict__ Qf, const T* __restrict__ Kf, const T* __restrict__ Vt,
                                                                const float* __restrict__ kbias, const int* __restrict__ klen,
                                                                const int* __restrict__ kfirst_, T* __restrict__ CTX, int B, int Sp, int nq,
                                                                int nkv, int causal, int ctx_gs, unsigned* gx_sat, int act_sc, int win = 0,
-                                                               const unsigned char* __restrict__ tile_flag = nullptr) {
+                                                               const unsigned char* __restrict__ tile_flag = nullptr,
+                                                               const float* __restrict__ rpb = nullptr) {
     static_assert(!SPLIT || sizeof(T) == 4, "split units live in the fp32 layouts");
+    static_assert(!RPB || (D == 64 && !WIN), "the relative-position bias exists at head_dim 64 without a window");
     typedef typename GqaFrag<SPLIT, T>::type frag_t;
     constexpr int NS = D / 16, ND = D / 32;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -515,6 +548,9 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
     }
     const int kfirst = kfirst_[b];
     const int foff = 8 * h;
+    // RPB: the lane's window into its head's table at key 0: entry (0 + foff) - (q0 + c) + Sp - 1 >= 0; the last one read is
+    // (Sp - 32) + 16 + 8 + 7 - 0 + Sp - 1 = 2 Sp - 2 < 2 Sp
+    [[maybe_unused]] const float* __restrict__ rp = RPB ? rpb + (size_t)hq * 2 * Sp + (foff - (q0 + c) + Sp - 1) : nullptr;
 
     frag_t qf[NS];
 #pragma unroll
@@ -536,6 +572,12 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
         for (int a = 0; a < ND; ++a)
 #pragma unroll
             for (int t = 0; t < 2; ++t) vt[a][t] = *reinterpret_cast<const frag_t*>(Vp + ((size_t)kt * ND * 2 + a * 2 + t) * 512);
+        const int k0 = kt * 32;
+        [[maybe_unused]] float rb[RPB ? 16 : 1];
+        if constexpr (RPB) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) rb[i] = rp[k0 + 16 * (i >> 3) + (i & 7)];
+        }
         // S^T = K Q^T ; reg i <-> key k0 + 16*(i>>3) + 8h + (i&7), column = query c
         f32x16 sacc;
 #pragma unroll
@@ -547,7 +589,10 @@ __global__ __launch_bounds__(256, SPLIT ? 1 : 2) void attn_gqa_mfma_kernel(const
         float sv[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) sv[i] = sacc[i];
-        const int k0 = kt * 32;
+        if constexpr (RPB) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) sv[i] += rb[i];
+        }
         if (k0 + 32 > kfirst) {                                             // wave-uniform: tile holds masked keys
             const f32x4 b0 = *reinterpret_cast<const f32x4*>(kb + k0 + foff);
             const f32x4 b1 = *reinterpret_cast<const f32x4*>(kb + k0 + foff + 4);
@@ -660,9 +705,14 @@ template <typename T, bool SPLIT = false> const char* launch_layout_t(hipStream_
 }
 template <typename T, bool SPLIT = false> const char* launch_gqa_t(hipStream_t st, const void* Qf, const void* Kf, const void* Vt, const float* kbias, const int* klen,
                                                const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0, int window = 0,
-                                               const unsigned char* tile_flag = nullptr) {
+                                               const unsigned char* tile_flag = nullptr, const float* rpb = nullptr) {
     const int nt = Sp / 32, nqb = (nt + 3) / 4, per = (nq / nkv) * nqb, bg8 = (B * nkv + 7) / 8 * 8;
     const dim3 grid(per * bg8), block(256);
+    if (rpb) {                  // T5's relative-position bias (head_dim 64, bidirectional, no window)
+        if (d != 64 || causal || window > 0) return "attention_gqa_mfma: the relative-position bias takes head_dim 64, no causal mask and no window";
+        hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, false, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc(), 0, tile_flag, rpb);
+        return nullptr;
+    }
     if (window > 0) {           // sliding window (ModernBERT, head_dim 64, bidirectional)
         if (d != 64 || causal) return "attention_gqa_mfma: the windowed kernel takes head_dim 64 and no causal mask";
         hipLaunchKernelGGL((attn_gqa_mfma_kernel<T, 64, SPLIT, true>), grid, block, 0, st, (const T*)Qf, (const T*)Kf, (const T*)Vt, kbias, klen, kfirst, (T*)CTX, B, Sp, nq, nkv, 0, ctx_gs, ctx_gs == 2 ? glc_gx_sat_ptr() : nullptr, glc_gx_act_sc(), window, tile_flag);
@@ -690,12 +740,12 @@ const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, co
 // MFMA grouped-query attention on the fragment-major operands written by glc_launch_qkv_layout.  CTX [B*Sp, nq*d] row-major.
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs,
-                                          int window, const unsigned char* tile_flag) {
+                                          int window, const unsigned char* tile_flag, const float* rpb) {
     if (!Qf || !Kf || !Vt || !kbias || !klen || !kfirst || !CTX || B <= 0 || Sp <= 0 || Sp % 64 || nq <= 0 || nkv <= 0 || nq % nkv ||
         (d != 64 && d != 128) || window < 0)
         return "attention_gqa_mfma: bad args";
-    if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag);
-    if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag);
-    if (dtype == GLC_DT_F32) return launch_gqa_t<float, true>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, ctx_gs, window, tile_flag);   // split-f16 units
+    if (dtype == GLC_DT_BF16) return launch_gqa_t<bf16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag, rpb);
+    if (dtype == GLC_DT_F16) return launch_gqa_t<f16_t>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, 0, window, tile_flag, rpb);
+    if (dtype == GLC_DT_F32) return launch_gqa_t<float, true>(st, Qf, Kf, Vt, kbias, klen, kfirst, CTX, B, Sp, nq, nkv, d, causal, ctx_gs, window, tile_flag, rpb);   // split-f16 units
     return "attention_gqa_mfma: bad dtype";
 }

@@ -124,8 +124,8 @@ template <class T> T* upload_table(glc_engine* e, const std::vector<T>& t, const
 // decoder / ModernBERT: one cos / sin table per (Sp, theta); ModernBERT's global and local layers use two bases
 bool build_rope_tables(glc_engine* e, int Sp) {
     const glc_model_config& c = e->cfg;
-    if (c.backbone == GLC_BACKBONE_BERT) {
-        // no rotation on this backbone: the layout passes get a table of cos = 1, sin = 0 (x 1 - y 0 = x, exact), filed under base 0
+    if (c.backbone == GLC_BACKBONE_BERT || c.backbone == GLC_BACKBONE_T5) {
+        // no rotation on these backbones: the layout passes get a table of cos = 1, sin = 0 (x 1 - y 0 = x, exact), filed under base 0
         if (e->ropes.count({Sp, 0.f})) return true;
         std::vector<float> t((size_t)Sp * (c.head_dim / 2) * 2);
         for (size_t i = 0; i < t.size(); i += 2) { t[i] = 1.f; t[i + 1] = 0.f; }
@@ -151,6 +151,22 @@ bool build_rope_tables(glc_engine* e, int Sp) {
         if (!d) return false;
         e->ropes[{Sp, theta}] = d;
     }
+    return true;
+}
+
+// T5: the relative-position bias of one padded length, rpb [t5_heads][2 Sp] fp32 in the log2 units of the exp2 softmax:
+// rel_bias[bucket(delta), h] log2(e) at entry delta + Sp - 1, delta = key - query (T5:264-281 compute_bias; the last entry of a head is never read)
+bool build_rpb_table(glc_engine* e, int Sp) {
+    if (e->rpbs.count(Sp)) return true;
+    const glc_model_config& c = e->cfg;
+    std::vector<int32_t> bk(2 * Sp - 1);
+    glc_t5_bucket_table(Sp, c.rel_buckets, c.rel_max_distance, bk.data());
+    std::vector<float> t((size_t)e->t5_heads * 2 * Sp, 0.f);
+    for (int h = 0; h < c.heads; ++h)
+        for (int j = 0; j < 2 * Sp - 1; ++j) t[(size_t)h * 2 * Sp + j] = e->rel_bias[(size_t)bk[j] * c.heads + h] * 1.4426950408889634f;
+    float* d = upload_table(e, t, "relative-position bias table");
+    if (!d) return false;
+    e->rpbs[Sp] = d;
     return true;
 }
 
@@ -212,8 +228,9 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     }
     const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
     const size_t es = esize(e->dtype);
-    const bool bert = c.backbone == GLC_BACKBONE_BERT;
-    const bool dec = c.backbone == GLC_BACKBONE_DECODER || c.backbone == GLC_BACKBONE_MODERNBERT || bert;    // (same workspace)
+    const bool bert = c.backbone == GLC_BACKBONE_BERT, t5 = c.backbone == GLC_BACKBONE_T5;
+    const bool dec = c.backbone == GLC_BACKBONE_DECODER || c.backbone == GLC_BACKBONE_MODERNBERT || bert || t5;    // (same workspace)
+    const int nh_ws = t5 ? e->t5_heads : c.heads, nkv_ws = t5 ? e->t5_heads : c.kv_heads;      // (T5: the head count the kernels run)
     if (Mpad > e->capM) {
         const size_t rows_h = (size_t)Mpad * c.hidden * es;
         if (!regrow(e, e->X, rows_h) || !regrow(e, e->H1, rows_h) || !regrow(e, e->FF, (size_t)Mpad * c.inter * es) ||
@@ -221,12 +238,12 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
         // (mean, rstd) or (0, rstd) per row of the two residual-stream buffers + the producers' partials (small; DeBERTa keeps them whether or not
         // the fold is switched on: glc_debug_set_ln_fused; the decoder's RMSNorm fold exists in the fp32 mode only)
         if (bert && !regrow(e, e->pos_ids, (size_t)Mpad * sizeof(int))) return false;
-        if ((!dec || e->dtype == GLC_F32) && !bert) {      // (BERT: no norm fold)
+        if ((!dec || e->dtype == GLC_F32) && !bert && !t5) {      // (BERT, T5: no norm fold)
             if (!regrow(e, e->statsA, (size_t)Mpad * sizeof(float2)) || !regrow(e, e->statsB, (size_t)Mpad * sizeof(float2)) ||
                 !regrow(e, e->ln_part, (size_t)Mpad * ((c.hidden + 63) / 64) * sizeof(float2))) return false;
         }
         if (dec) {
-            const size_t nqd = (size_t)c.heads * c.head_dim, nkvd = (size_t)c.kv_heads * c.head_dim;
+            const size_t nqd = (size_t)nh_ws * c.head_dim, nkvd = (size_t)nkv_ws * c.head_dim;
             if (!regrow(e, e->X2, rows_h) || !regrow(e, e->QKV, (size_t)Mpad * (nqd + 2 * nkvd) * es) || !regrow(e, e->CTX, (size_t)Mpad * nqd * es)) return false;
             if (e->dtype != GLC_F32 || e->dec_split) {          // fragment-major operands of the MFMA attention kernel (fp32 mode: split-f16 units, same bytes)
                 if (!regrow(e, e->Qh, (size_t)Mpad * nqd * es) || !regrow(e, e->Kh, (size_t)Mpad * nkvd * es) || !regrow(e, e->Vt, (size_t)Mpad * nkvd * es)) return false;
@@ -262,7 +279,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     // context rows are heads * head_dim wide, which need not be the hidden size
     const int rsel = round_up(B * (1 + (C > 0 ? C : 0)), 256);
     if (rsel > e->capSel && !bert) {       // (BERT: no pruned last layer)
-        const size_t wide = dec ? std::max((size_t)c.hidden, (size_t)c.heads * c.head_dim) : (size_t)c.hidden;
+        const size_t wide = dec ? std::max((size_t)c.hidden, (size_t)nh_ws * c.head_dim) : (size_t)c.hidden;
         for (void** b : {&e->Xs, &e->CTXs, &e->T1s, &e->H1s}) if (!regrow(e, *b, (size_t)rsel * wide * es)) return false;
         if (!dec && !regrow(e, e->Qs, (size_t)rsel * c.hidden * es)) return false;
         if (dec && !regrow(e, e->GUs, (size_t)rsel * 2 * c.inter * es)) return false;
@@ -274,6 +291,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
         if (!regrow(e, e->tile_flag, nf)) return false;
         e->capFlag = nf;
     }
+    if (t5 && !build_rpb_table(e, Sp)) return false;
     if (dec) return build_rope_tables(e, Sp);
     return build_position_tables(e, Sp);
 }
@@ -529,6 +547,8 @@ struct Glu {
     const char* (*rows_gs)(hipStream_t, const float*, void*, size_t, int);            // ... over plain fp32 GU rows, group-split output
 };
 const Glu kSwiGlu{EPI_SWIGLU, glc_launch_swiglu, glc_launch_swiglu_gs}, kGeGlu{EPI_GEGLU, glc_launch_geglu, glc_launch_geglu_gs};
+// T5's gated tanh-GELU: a row pass only (the backbone runs with fused_swiglu = false; there is no tanh-GELU GEMM epilogue, so epi is never read)
+const Glu kGeGluTanh{EPI_GEGLU, glc_launch_geglu_tanh, glc_launch_geglu_tanh_gs};
 
 bool gated_ffn(glc_engine* e, const Glu& glu, GemmArgs f1, bool gs, const GemmGs& gemm_gs, int M) {
     hipStream_t st = e->stream;
@@ -823,6 +843,88 @@ bool run_forward_modernbert(glc_engine* e, const int64_t* ids, const int64_t* ma
     return forward_epilogue(e, e->H1, false, B, S, C, d_logits);
 }
 
+// T5 / mT5 backbone (transformers 5.15 models/t5/modeling_t5.py, the encoder T5Stack, cited as T5:<line>): one launch sequence per batch.  The
+// decoder's pre-norm residual stream on bias-free RMSNorms (T5LayerNorm, T5:50-71) and projections, without its norm fold and MX pipeline:
+// x += O(Attn(RMS(x))) (T5LayerSelfAttention, T5:392-400), x += wo(gelu_new(wi_0 RMS(x)) * wi_1 RMS(x)) (T5LayerFF + T5DenseGatedActDense,
+// T5:97-141), final_layer_norm behind the last block (T5:744).  The attention has no rotation (the layout pass gets cos = 1 / sin = 0), no
+// 1/sqrt(d) scale (T5Attention.scaling = 1.0: qscale = log2(e) alone) and adds layer 0's relative-position bias, shared by every
+// layer (T5:335-348, T5:738-740), ahead of the additive key mask: the RPB instantiations of the two attention kernels (decoder.hip).
+// nh = t5_heads: cfg.heads rounded up to even, the extra head's weights zero (create_t5).  16-bit modes and the fp32 mode's small / odd
+// shapes run plain rows of T; the fp32 mode runs the group-split pipeline under ModernBERT's conditions with the norms as kernels of their
+// own.  The last layer is pruned as on the other pre-norm backbones (run_pruned_tail).  No MX pipeline.
+bool run_forward_t5(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, int C, float* d_logits) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, nh = e->t5_heads, d = c.head_dim, L = c.layers, NQ = nh * d;
+    const int Sp = round_up(S, 64), M = B * Sp, Mpad = round_up(M, 256);
+    hipStream_t st = e->stream;
+    const int dt = e->dtype;
+    if (!forward_prologue(e, ids, mask, B, S)) return false;
+    void *X = e->X, *Xn = e->X2;
+    { Prof p(e, PC_EMBED);                                                                                                  // T5:678 embed_tokens: no scale, no norm
+      KCHK(glc_launch_embed_plain(st, dt, ids, mask, e->emb, X, e->kbias, B, S, Sp, H, c.vocab, c.pad_id), false); }
+    if (!dump_hidden(e, 0, X, M)) return false;
+    const float qscale = 1.4426950408889634f;                            // log2(e) for the exp2 softmax; T5 does not scale its scores
+    const bool mfma = (dt != GLC_F32 || e->dec_split) && e->attn_impl != 1;
+    bool gs = false;
+    if (dt == GLC_F32 && e->gs_mode > 0 && e->w_presplit && e->dec_split && mfma && !e->keep_hidden && H % 256 == 0 && (2 * I) % 256 == 0 &&
+        (3 * NQ) % 256 == 0 && NQ % 32 == 0 && I % 32 == 0) {
+        GemmArgs t; t.Mpad = Mpad; t.N = H; t.K = H;
+        gs = e->gs_mode == 2 || !glc_gemm_small_m(t);
+    }
+    e->last_gs = gs;
+    e->last_lnf = false; e->last_mx = false; e->last_mx_attn = false; e->last_rope_epi = false; e->last_mx128 = 0; e->last_pruned = false;
+    const GemmGs gemm_gs{st, false, M};
+    const PrunedTail pt = pruned_tail(e, B, C);
+    const float* cs = e->ropes[{Sp, 0.f}];
+    const float* rpb = e->rpbs[Sp];
+    auto norm = [&](const void* src, const float* gain) -> const char* {      // H1 = RMS(src) (group-split rows in the gs pipeline)
+        return gs ? glc_launch_rmsnorm_gs(st, (const float*)src, e->H1, gain, c.ln_eps, M, H) : glc_launch_rmsnorm(st, dt, src, e->H1, gain, c.ln_eps, M, H);
+    };
+    for (int l = 0; l < L; ++l) {
+        const DecLayerW& w = e->dlayers[l];
+        const bool last = pt.on && l == L - 1;        // pruned (see run_pruned_tail): the residual rows the head reads, then K / V on every row
+        const unsigned char* flag = last && mfma ? e->tile_flag : nullptr;
+        if (last) {
+            Prof p(e, PC_LAST);
+            HIPCHK(hipMemsetAsync(e->tile_flag, 0, (size_t)Mpad >> 5, st), false);
+            KCHK(glc_launch_gather_rows(st, dt, X, e->cls_pos, class_cap(e), e->Xs, e->sel_b, e->sel_q, e->tile_flag, B, Sp, H, pt.Cc, pt.klen), false);
+        }
+        { Prof p(e, last ? PC_LAST : PC_LN); KCHK(norm(X, w.ln1), false); }                                               // T5:392
+        GemmArgs g;
+        g.A = e->H1; g.W = w.Wqkv; g.bias = nullptr; g.C = e->QKV; g.Mpad = Mpad; g.N = 3 * NQ; g.K = H; g.gs_c_plain = 1;
+        { Prof p(e, last ? PC_LAST : PC_QKV);
+          KCHK(gs ? gemm_gs(EPI_BIAS, g) : launch_gemm_auto(e, dt, EPI_BIAS, g), false);                                    // T5:304-326 q / k / v
+          if (mfma) KCHK(glc_launch_qkv_layout(st, dt, e->QKV, cs, e->Qh, e->Kh, e->Vt, B, Sp, nh, nh, d, qscale), false);
+          else KCHK(glc_launch_rope_qk(st, dt, e->QKV, cs, M, Sp, nh, nh, d, qscale), false); }
+        { Prof p(e, last ? PC_LAST : PC_ATTN);                                                                             // T5:335-364
+          if (mfma) KCHK(glc_launch_attention_gqa_mfma(st, dt, e->Qh, e->Kh, e->Vt, e->kbias, e->klen, e->kfirst, e->CTX, B, Sp, nh, nh, d, 0, last ? 0 : (gs ? 1 : 0), 0, flag, rpb), false);
+          else KCHK(glc_launch_attention_gqa(st, dt, 1, e->QKV, e->kbias, e->klen, e->CTX, B, Sp, nh, nh, d, 0, 0, rpb), false); }
+        if (last) {
+            { Prof p(e, PC_LAST);
+            KCHK(glc_launch_gather_sel(st, dt, e->CTX, e->sel_b, e->sel_q, e->CTXs, pt.R, Sp, NQ), false);
+            auto norm_r = [&](const void* src, void* dst, const float* gain) { return glc_launch_rmsnorm(st, dt, src, dst, gain, c.ln_eps, pt.R, H); };
+            if (!run_pruned_tail(e, pt, w, kGeGluTanh, NQ, norm_r)) return false; }                                        // T5:367-744 on R rows
+            return forward_epilogue(e, e->H1s, true, B, S, C, d_logits);
+        }
+        GemmArgs o;
+        o.A = e->CTX; o.W = w.Wo; o.bias = nullptr; o.C = Xn; o.resid = X; o.Mpad = Mpad; o.N = H; o.K = NQ; o.gs_resid_plain = 1;
+        { Prof p(e, PC_ATTN_OUT); KCHK(gs ? gemm_gs(EPI_RESID, o) : launch_gemm_auto(e, dt, EPI_RESID, o), false); }      // T5:367, :400
+        std::swap(X, Xn);
+        { Prof p(e, PC_LN); KCHK(norm(X, w.ln2), false); }                                                                 // T5:138
+        GemmArgs f1;
+        f1.A = e->H1; f1.W = w.Wgu; f1.bias = nullptr; f1.Mpad = Mpad; f1.N = 2 * I; f1.K = H;
+        if (!gated_ffn(e, kGeGluTanh, f1, gs, gemm_gs, M)) return false;                                                   // T5:107-109 gelu_new(wi_0) * wi_1
+        GemmArgs f2;
+        f2.A = e->FF; f2.W = w.Wd; f2.bias = nullptr; f2.C = Xn; f2.resid = X; f2.Mpad = Mpad; f2.N = H; f2.K = I; f2.gs_resid_plain = 1;
+        { Prof p(e, PC_FFN2); KCHK(gs ? gemm_gs(EPI_RESID, f2) : launch_gemm_auto(e, dt, EPI_RESID, f2), false); }        // T5:122, :140
+        std::swap(X, Xn);
+        if (l + 1 < L && !dump_hidden(e, l + 1, X, M)) return false;
+    }
+    { Prof p(e, PC_LN); KCHK(glc_launch_rmsnorm(st, dt, X, e->H1, e->final_norm, c.ln_eps, M, H), false); }                // T5:744
+    if (!dump_hidden(e, L, e->H1, M)) return false;
+    return forward_epilogue(e, e->H1, false, B, S, C, d_logits);
+}
+
 // BERT / RoBERTa / XLM-R backbone (transformers models/bert/modeling_bert.py): one launch sequence per batch.  Post-LayerNorm blocks as
 // DeBERTa's, on the decoder's workspace and attention kernels: word + absolute position + token-type embedding under a LayerNorm (rows.hip
 // embed_abs), then per layer QKV = x Wqkv^T + b, plain bidirectional attention (scores / sqrt(64), additive key mask; the layout pass with a
@@ -1070,6 +1172,7 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
     case GLC_BACKBONE_DECODER: return run_forward_decoder(e, ids, mask, B, S, C, d_logits);
     case GLC_BACKBONE_MODERNBERT: return run_forward_modernbert(e, ids, mask, B, S, C, d_logits);
     case GLC_BACKBONE_BERT: return run_forward_bert(e, ids, mask, B, S, C, d_logits);
+    case GLC_BACKBONE_T5: return run_forward_t5(e, ids, mask, B, S, C, d_logits);
     default: return run_forward_deberta(e, ids, mask, B, S, C, d_logits);
     }
 }
@@ -1180,7 +1283,8 @@ bool graph_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B
 // copy goes up in one piece) or the FFN's input weight (the gated FFNs' [first | second] rows in one piece)
 size_t staging_floats(const glc_model_config& c) {
     const size_t H = c.hidden, I = c.inter;
-    const size_t qkv = c.backbone == GLC_BACKBONE_DECODER ? (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim : 3 * H;
+    const size_t qkv = c.backbone == GLC_BACKBONE_DECODER ? (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim
+                     : c.backbone == GLC_BACKBONE_T5 ? 3 * (size_t)((c.heads + 1) / 2 * 2) * c.head_dim : 3 * H;
     const size_t ffn = c.backbone == GLC_BACKBONE_DEBERTA || c.backbone == GLC_BACKBONE_BERT ? I : 2 * I;
     const size_t pos = c.backbone == GLC_BACKBONE_BERT ? (size_t)c.max_positions : 0;
     return std::max({(size_t)c.vocab * H, qkv * H, ffn * H, pos * H});
@@ -1312,6 +1416,36 @@ bool create_modernbert(glc_engine* e, const float* const* tensors, float* stagin
         for (int i = 0; i < H; ++i) e->mb_ln_bound = fmaxf(e->mb_ln_bound, fmaxf(attn_norm ? fabsf(attn_norm[i]) : fabsf(tensors[1][i]), fabsf(t[2][i])) * sqrtf((float)H));
     }
     e->final_norm = upload_f32(e, tensors[L > 0 ? glc_mb_layer_base(L) : 2], H);
+    return e->final_norm != nullptr;
+}
+
+// T5 backbone: upload + convert weights (include/gliclass_hip.h tensor order).  rel_bias stays on the host (build_rpb_table turns it into
+// one device table per padded length).  Per layer the fused Wqkv (rows q | k | v), o, the fused [wi_0 | wi_1] and wo as they come — except
+// with an odd head count: the kernels run t5_heads = heads + 1 heads, so q, k and v each get 64 zero rows behind their own and o 64 zero
+// columns (the extra head attends uniformly over zero values and multiplies zero weights: it adds exactly 0).
+bool create_t5(glc_engine* e, const float* const* tensors, float* staging) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden, I = c.inter, L = c.layers, d = c.head_dim;
+    const size_t IN = (size_t)c.heads * d, NQ = (size_t)e->t5_heads * d, IH = (size_t)I * H;
+    e->rel_bias.assign(tensors[1], tensors[1] + (size_t)c.rel_buckets * c.heads);
+    e->dlayers.resize(L);
+    std::vector<float> qkv_host, o_host;
+    for (int l = 0; l < L; ++l) {
+        const float* const* t = tensors + GLC_T5_TENSORS_FIXED + GLC_T5_TENSORS_PER_LAYER * l;      // t: ln1 Wqkv Wo ln2 Wgu Wd
+        DecLayerW& w = e->dlayers[l];
+        const float *wqkv = t[1], *wo = t[2];
+        if (NQ != IN) {
+            qkv_host.assign(3 * NQ * H, 0.f); o_host.assign((size_t)H * NQ, 0.f);
+            for (int p = 0; p < 3; ++p) memcpy(qkv_host.data() + p * NQ * H, t[1] + p * IN * H, IN * H * sizeof(float));
+            for (int r = 0; r < H; ++r) memcpy(o_host.data() + r * NQ, t[2] + r * IN, IN * sizeof(float));
+            wqkv = qkv_host.data(); wo = o_host.data();
+        }
+        if (!upload_projections(e, staging, {{&w.Wqkv, {{wqkv, 3 * NQ * H}}}, {&w.Wo, {{wo, (size_t)H * NQ}}}, {&w.Wgu, {{t[4], 2 * IH}}}, {&w.Wd, {{t[5], IH}}}})) return false;
+        w.ln1 = upload_f32(e, t[0], H); w.ln2 = upload_f32(e, t[3], H);
+        if (!w.ln1 || !w.ln2) return false;
+        if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err("sync failed"); return false; }   // the padded host buffers are reused
+    }
+    e->final_norm = upload_f32(e, tensors[GLC_T5_TENSORS_FIXED + GLC_T5_TENSORS_PER_LAYER * L], H);
     return e->final_norm != nullptr;
 }
 
@@ -1517,6 +1651,24 @@ void glc_delta_table(int S, int bucket_size, int max_position, int32_t* out) {
     }
 }
 
+/* modeling_t5.py T5Attention._relative_position_bucket (T5:217-262) with bidirectional=True, relative_position = key - query; float32
+ * arithmetic like torch: log(rp / max_exact) / log(max_distance / max_exact) * (half - max_exact), truncated (.to(torch.long)) */
+void glc_t5_bucket_table(int S, int num_buckets, int max_distance, int32_t* out) {
+    const int half = num_buckets / 2, max_exact = half / 2;
+    const float den = (float)log((double)max_distance / (double)max_exact);      // (math.log of two Python numbers, then a float32 operand)
+    for (int r = -(S - 1); r <= S - 1; ++r) {
+        const int ar = r < 0 ? -r : r;
+        int bk = r > 0 ? half : 0;
+        if (ar < max_exact) bk += ar;
+        else {
+            const float lg = logf((float)ar / (float)max_exact) / den * (float)(half - max_exact);
+            const int big = max_exact + (int)lg;
+            bk += big < half - 1 ? big : half - 1;
+        }
+        out[r + S - 1] = bk;
+    }
+}
+
 glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* tensors, int n_tensors, int device, int dtype) {
     if (!cfg || !tensors) { glc_set_err("engine_create: null argument"); return nullptr; }
     if (dtype != GLC_F32 && dtype != GLC_BF16 && dtype != GLC_F16) { glc_set_err("engine_create: bad dtype"); return nullptr; }
@@ -1525,7 +1677,12 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (n_tensors != glc_num_tensors_cfg(cfg)) { glc_set_err("engine_create: wrong tensor count"); return nullptr; }
     for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { glc_set_err("engine_create: null tensor"); return nullptr; }
     const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT, bert = cfg->backbone == GLC_BACKBONE_BERT;
-    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb && !bert) { glc_set_err("engine_create: unknown backbone"); return nullptr; }
+    const bool t5 = cfg->backbone == GLC_BACKBONE_T5;
+    if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb && !bert && !t5) { glc_set_err("engine_create: unknown backbone"); return nullptr; }
+    if (t5 && (cfg->head_dim != 64 || cfg->heads < 1 || cfg->layers < 1 || cfg->rel_buckets < 4 || cfg->rel_buckets % 4 || cfg->rel_buckets > (1 << 16) ||
+               cfg->rel_max_distance <= cfg->rel_buckets / 4 || cfg->pad_id < 0 || cfg->pad_id >= cfg->vocab)) {
+        glc_set_err("engine_create: T5 backbone needs head_dim 64, rel_buckets a multiple of 4 and rel_max_distance > rel_buckets / 4"); return nullptr;
+    }
     if (bert && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64 || cfg->layers < 1 || cfg->type_vocab < 1 || cfg->pos_offset < 0 || cfg->pad_id < 0 ||
                  cfg->pad_id >= cfg->vocab || (cfg->pos_offset != 0 && cfg->pos_offset != cfg->pad_id + 1) || cfg->max_positions - cfg->pos_offset < 1)) {
         glc_set_err("engine_create: BERT backbone needs head_dim 64, type_vocab >= 1, pos_offset 0 or pad_id + 1 and max_positions > pos_offset"); return nullptr;
@@ -1534,7 +1691,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
                cfg->rope_theta <= 1.f || (cfg->local_window > 0 && cfg->rope_theta_local <= 1.f))) {
         glc_set_err("engine_create: ModernBERT backbone needs head_dim 64, local_window >= 0, global_every >= 1 and RoPE bases > 1"); return nullptr;
     }
-    if (!dec && !mb && !bert && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { glc_set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
+    if (!dec && !mb && !bert && !t5 && (cfg->head_dim != 64 || cfg->hidden != cfg->heads * 64)) { glc_set_err("engine_create: head_dim must be 64 (all DeBERTa-v3 backbones)"); return nullptr; }
     if (dec && ((cfg->head_dim != 64 && cfg->head_dim != 128) || cfg->heads <= 0 || cfg->kv_heads < 0 ||
                 cfg->heads % (cfg->kv_heads > 0 ? cfg->kv_heads : cfg->heads) || cfg->rope_theta <= 1.f)) {
         glc_set_err("engine_create: decoder backbone needs head_dim 64 or 128, heads % kv_heads == 0 and rope_theta > 1"); return nullptr;
@@ -1556,9 +1713,10 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     glc_engine* e = new glc_engine();
     e->cfg = *cfg; e->dtype = dtype; e->device = device;
     if (e->cfg.kv_heads <= 0) e->cfg.kv_heads = e->cfg.heads;
+    if (t5) e->t5_heads = (cfg->heads + 1) / 2 * 2;
     if (const char* pv = getenv("GLICLASS_PRUNE_LAST")) e->prune_last = atoi(pv) != 0;
     { const char* gv = getenv("GLICLASS_F32_GEMM"); e->w_presplit = !(gv && !strcmp(gv, "native")) ; }   // hidden and inter are multiples of 128 (checked above)
-    { const char* av = getenv("GLICLASS_F32_ATTN"); e->dec_split = dtype == GLC_F32 && (dec || mb || bert) && !(av && !strcmp(av, "native")); }
+    { const char* av = getenv("GLICLASS_F32_ATTN"); e->dec_split = dtype == GLC_F32 && (dec || mb || bert || t5) && !(av && !strcmp(av, "native")); }
     { const char* av = getenv("GLICLASS_F32_ATTN"); e->attn_split = dtype == GLC_F32 && cfg->backbone == GLC_BACKBONE_DEBERTA && !(av && !strcmp(av, "native")); }
     if (const char* lv = glc_dev_env("GLC_LNF")) e->ln_fused = atoi(lv) != 0;      // developer A/B switch
     // MX cross-term pipeline (docs/LOG_r01-r05.md §3e) — the default arithmetic of the large forwards of the default mode since round 3: the
@@ -1570,7 +1728,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
         e->mx_env = !mv ? 0 : !strcmp(mv, "0") ? 1 : !strcmp(mv, "build") ? 2 : 0;
         const bool eligible = dec ? (dtype == GLC_F32 && e->w_presplit && e->dec_split && e->ln_fused && cfg->hidden % 256 == 0 && (2 * cfg->inter) % 256 == 0 && cfg->inter % 32 == 0)
                                   : (dtype == GLC_F32 && e->w_presplit && e->attn_split && e->ln_fused && cfg->hidden % 256 == 0 && cfg->inter % 256 == 0 && cfg->layers >= 2);
-        e->mx_built = eligible && !mb && !bert && !(mv && !strcmp(mv, "0"));      // (ModernBERT: opt-in, glc_engine_enable_mx; BERT: no MX pipeline)
+        e->mx_built = eligible && !mb && !bert && !t5 && !(mv && !strcmp(mv, "0"));      // (ModernBERT: opt-in, glc_engine_enable_mx; BERT, T5: no MX pipeline)
         e->mx = e->mx_built && !(mv && !strcmp(mv, "build"));
         if (const char* av = glc_dev_env("GLC_MX_ATTN")) e->mx_attn = atoi(av) != 0;      // developer A/B switch
         if (const char* av = glc_dev_env("GLC_DEC_ROPE_EPI")) e->dec_rope_epi = atoi(av) != 0;      // developer A/B switch
@@ -1593,7 +1751,7 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     e->emb = dmalloc(e, nemb * esize(dtype), false);
     if (!e->emb || !upload_as(e, tensors[0], nemb, e->emb, staging)) return fail();
     const bool loaded = dec ? create_decoder(e, tensors, staging) : mb ? create_modernbert(e, tensors, staging) : bert ? create_bert(e, tensors, staging)
-                                                                                                                  : create_deberta(e, tensors, staging);
+                            : t5 ? create_t5(e, tensors, staging) : create_deberta(e, tensors, staging);
     if (!loaded || !upload_head(e, tensors + n_tensors - GLC_TENSORS_HEAD - glc_num_scorer_tensors(cfg->scorer))) return fail();
     // ModernBERT: the MX pipeline is opt-in; the environment makes the call glc_engine_enable_mx documents (read once, here).  An engine it does
     // not fit stays as it is: not an error.
@@ -1618,6 +1776,7 @@ int glc_engine_enable_mx(glc_engine* e) {
     if (!e) { glc_set_err("enable_mx: null engine"); return -1; }
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->cfg.backbone == GLC_BACKBONE_BERT) { glc_set_err("enable_mx: the BERT backbone has no MX pipeline (its forwards run the split-f16 / 16-bit kernels)"); return -1; }
+    if (e->cfg.backbone == GLC_BACKBONE_T5) { glc_set_err("enable_mx: the T5 backbone has no MX pipeline (its forwards run the split-f16 / 16-bit kernels)"); return -1; }
     if (e->cfg.backbone != GLC_BACKBONE_MODERNBERT) {
         if (e->mx_built) return 0;
         glc_set_err("enable_mx: the MX pipeline is not available to this engine (shapes, dtype, or GLICLASS_MX=0 at creation)"); return -1;
@@ -2089,7 +2248,7 @@ int glc_engine_set_mx_small_forwards(glc_engine* e, int mode) {
     if (mode < 0 || mode > 2) { glc_set_err("set_mx_small_forwards: 0 off, 1 auto, 2 whenever the shapes allow"); return -1; }
     if (mode > 0 && e->cfg.backbone != GLC_BACKBONE_DEBERTA) {
         glc_set_err(std::string("set_mx_small_forwards: the 128 tile has no epilogue of the ") +
-                    (e->cfg.backbone == GLC_BACKBONE_DECODER ? "decoder" : e->cfg.backbone == GLC_BACKBONE_BERT ? "bert" : "modernbert") + " backbone (DeBERTa engines only)");
+                    (e->cfg.backbone == GLC_BACKBONE_DECODER ? "decoder" : e->cfg.backbone == GLC_BACKBONE_BERT ? "bert" : e->cfg.backbone == GLC_BACKBONE_T5 ? "t5" : "modernbert") + " backbone (DeBERTa engines only)");
         return -1;
     }
     std::lock_guard<std::mutex> lk(e->mu);

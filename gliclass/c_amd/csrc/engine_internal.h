@@ -143,6 +143,10 @@ struct glc_engine {
     // BERT backbone (layers, eln_g / eln_b as DeBERTa's; the decoder's workspace): the position table [max_positions, H] and row 0 of the
     // token-type table as T, and the position ids [capM] of the forward (rows.hip pos_ids_kernel)
     void *pos_emb = nullptr, *type_emb = nullptr; int* pos_ids = nullptr;
+    // T5 backbone (dlayers, final_norm; the decoder's workspace): the bias table rel_bias [rel_buckets, heads] as it came, the per-Sp device
+    // tables rpb [t5_heads][2 Sp] = rel_bias[bucket(delta), h] log2(e) at entry delta + Sp - 1 (build_rpb_table), and the head count the
+    // kernels run: cfg.heads rounded up to even (the fused QKV projection is a multiple of 128 wide), the extra head all zeros
+    std::vector<float> rel_bias; std::map<int, float*> rpbs; int t5_heads = 0;
     std::map<std::pair<int, float>, float*> ropes;                    // (Sp, theta) -> [Sp][d/2][cos,sin]
     void *QKV = nullptr, *GU = nullptr, *X2 = nullptr;                // decoder workspace: fused QKV rows, [gate|up] rows, second residual buffer
     bool fused_swiglu = false;                                        // Wgu rows interleaved 16 gate / 16 up: SwiGLU runs in the GEMM epilogue

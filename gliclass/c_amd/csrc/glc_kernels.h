@@ -296,6 +296,7 @@ const char* glc_launch_embed_plain(hipStream_t st, int dtype, const int64_t* ids
 const char* glc_launch_rmsnorm_gs(hipStream_t st, const float* X, void* Y, const float* w, float eps, int M, int H);
 const char* glc_launch_swiglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I);
 const char* glc_launch_geglu_gs(hipStream_t st, const float* GU, void* F, size_t M, int I);       // gelu(GU[m, i]) * GU[m, I + i] (ModernBERT)
+const char* glc_launch_geglu_tanh_gs(hipStream_t st, const float* GU, void* F, size_t M, int I);  // gelu_new(GU[m, i]) * GU[m, I + i] (T5 gated-gelu)
 const char* glc_launch_rmsnorm(hipStream_t st, int dtype, const void* X, void* Y, const float* w, float eps, int M, int H);
 // in-place rotate-half RoPE on the Q and K heads of QKV [M, (nq+2nkv) d]; cs = [Sp][d/2][cos,sin]; Q additionally * qscale
 // qn / kn (here and in the two layout passes below): gains [d] of Qwen3's per-head RMSNorm on the Q / K heads (eps its epsilon), applied before
@@ -306,9 +307,12 @@ const char* glc_launch_rope_qk(hipStream_t st, int dtype, void* QKV, const float
 const char* glc_launch_swiglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter = 0);   // inter: 16 gate / 16 up interleaved columns
 // F[m,i] = gelu(GU[m,i]) * GU[m,I+i] (ModernBERT's GeGLU on [input | gate]; erf GELU); inter as above
 const char* glc_launch_geglu(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter = 0);
+// T5's gated-gelu (modeling_t5.py T5DenseGatedActDense): gelu_new(GU[m, i]) * GU[m, I + i], the tanh form of GELU, on the fused [wi_0 | wi_1] rows
+const char* glc_launch_geglu_tanh(hipStream_t st, int dtype, const void* GU, void* F, size_t M, int I, int inter = 0);
 // grouped-query attention on the row-major fused QKV (Q pre-scaled by log2e/sqrt(d)); CTX [B*Sp, nq*d]; impl 1 = straightforward
 const char* glc_launch_attention_gqa(hipStream_t st, int dtype, int impl, const void* QKV, const float* kbias, const int* klen, void* CTX,
-                                     int B, int Sp, int nq, int nkv, int d, int causal, int window = 0);   // window > 0: keys |q - k| <= window only
+                                     int B, int Sp, int nq, int nkv, int d, int causal, int window = 0,    // window > 0: keys |q - k| <= window only
+                                     const float* rpb = nullptr);   // T5: [nq][2 Sp] relative-position bias in log2 units, entry (k - q) + Sp - 1; null = none
 // 16-bit MFMA path: RoPE + scale + fragment-major Q / K / V^T (layouts in decoder.hip), then the flash-style kernel
 const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, const float* cs, void* Qf, void* Kf, void* Vt, int B, int Sp,
                                   int nq, int nkv, int d, float qscale, const float* qn = nullptr, const float* kn = nullptr, float eps = 0.f);
@@ -318,7 +322,8 @@ const char* glc_launch_qkv_layout(hipStream_t st, int dtype, const void* QKV, co
 const char* glc_launch_attention_gqa_mfma(hipStream_t st, int dtype, const void* Qf, const void* Kf, const void* Vt, const float* kbias,
                                           const int* klen, const int* kfirst, void* CTX, int B, int Sp, int nq, int nkv, int d, int causal, int ctx_gs = 0,
                                           int window = 0,    // window > 0 (head_dim 64, not causal): keys |q - k| <= window only
-                                          const unsigned char* tile_flag = nullptr);
+                                          const unsigned char* tile_flag = nullptr,
+                                          const float* rpb = nullptr);   // T5's relative-position bias, as glc_launch_attention_gqa's (head_dim 64, not causal, no window)
 
 // MX pipeline (decoder_mx.hip, round 4): the fused fp32 projection -> RoPE + scale + MX tiles (f16 hi units + fp8 steps, 4 bytes per element),
 // and the grouped-query attention on them (a_hi*b_hi in f16 MFMAs + both cross terms in one block-scaled fp8 MFMA); CTX as GX rows

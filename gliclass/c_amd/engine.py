@@ -17,12 +17,20 @@ def to_c_config(cfg: GLiClassConfig) -> _lib.ModelConfig:
                             cfg.max_rel_pos, cfg.pad_id, cfg.cls_id, cfg.sep_id, cfg.class_token_index, cfg.text_token_index,
                             cfg.pooling, cfg.scorer, cfg.embed_class_token, cfg.normalize_features, cfg.backbone, cfg.kv_heads,
                             cfg.causal, cfg.ln_eps, cfg.logit_scale, cfg.rope_theta, cfg.local_window, cfg.global_every,
-                            cfg.rope_theta_local, cfg.qk_norm, cfg.attn_bias, cfg.max_positions, cfg.type_vocab, cfg.pos_offset)
+                            cfg.rope_theta_local, cfg.qk_norm, cfg.attn_bias, cfg.max_positions, cfg.type_vocab, cfg.pos_offset,
+                            cfg.rel_buckets, cfg.rel_max_distance)
 
 
 def delta_table(S, bucket_size=256, max_position=512):
     out = np.zeros(2 * S - 1, np.int32)
     _lib.hip().glc_delta_table(S, bucket_size, max_position, out.ctypes.data)
+    return out
+
+
+def t5_bucket_table(S, num_buckets=32, max_distance=128):
+    """T5's bidirectional relative-position bucket of delta = key - query for delta in [-(S-1), S-1] (host function of the engine library)"""
+    out = np.zeros(2 * S - 1, np.int32)
+    _lib.hip().glc_t5_bucket_table(S, num_buckets, max_distance, out.ctypes.data)
     return out
 
 

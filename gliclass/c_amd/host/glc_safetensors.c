@@ -6,8 +6,9 @@
  * config.json and the safetensors header (8-byte little-endian length, JSON {"name": {"dtype","shape","data_offsets"}},
  * raw little-endian tensor data); F32 / F16 / BF16 tensors are widened to fp32.
  *
- * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `Qwen3Model` / `LlamaModel` / `ModernBertModel` / `BertModel` / `RobertaModel` state_dict) under any of the prefixes GLiClass checkpoints use
- * (the BERT family's query / key / value projections are concatenated into the fused Wqkv of the tensor order);
+ * Tensor names are HF's (`DebertaV2Model` / `Qwen2Model` / `Qwen3Model` / `LlamaModel` / `ModernBertModel` / `BertModel` / `RobertaModel` / `T5EncoderModel` state_dict) under any of the prefixes GLiClass checkpoints use
+ * (the BERT family's query / key / value projections are concatenated into the fused Wqkv of the tensor order, and so are T5's q / k / v and
+ * its wi_0 / wi_1; a T5 checkpoint's decoder-side tensors are ignored);
  * configuration fields follow transformers' DebertaV2Config / Qwen2Config inside `encoder_config`, and the GLiClass
  * fields as restated in SURVEY.md §8a row a12 (class_token_index, text_token_index, pooling_strategy, scorer_type,
  * embed_class_token, normalize_features ...).  The GLiClass field names come from the upstream python package, which
@@ -103,13 +104,15 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
     c->pad_id = (int32_t)jnum(enc, "pad_token_id", 0);
     c->cls_id = (int32_t)jnum(enc, "cls_token_id", jnum(enc, "bos_token_id", 1));
     c->sep_id = (int32_t)jnum(enc, "sep_token_id", jnum(enc, "eos_token_id", 2));
-    c->hidden = (int32_t)jnum(enc, "hidden_size", 0);
-    c->layers = (int32_t)jnum(enc, "num_hidden_layers", 0);
-    c->heads = (int32_t)jnum(enc, "num_attention_heads", 0);
-    c->inter = (int32_t)jnum(enc, "intermediate_size", 0);
+    const int is_t5 = !strcmp(mt, "t5") || !strcmp(mt, "mt5");          /* T5Config names its dimensions d_model / num_layers / num_heads / d_ff / d_kv */
+    if (!strcmp(mt, "umt5")) REJECT("model_type 'umt5' is not implemented (a relative_attention_bias table per layer; t5 and mt5 share layer 0's)");
+    c->hidden = (int32_t)jnum(enc, is_t5 ? "d_model" : "hidden_size", 0);
+    c->layers = (int32_t)jnum(enc, is_t5 ? "num_layers" : "num_hidden_layers", 0);
+    c->heads = (int32_t)jnum(enc, is_t5 ? "num_heads" : "num_attention_heads", 0);
+    c->inter = (int32_t)jnum(enc, is_t5 ? "d_ff" : "intermediate_size", 0);
     c->vocab = (int32_t)jnum(root, "vocab_size", jnum(enc, "vocab_size", 0));
-    if (c->hidden <= 0 || c->layers <= 0 || c->heads <= 0 || c->inter <= 0 || c->hidden % c->heads) REJECT("missing or inconsistent backbone dimensions");
-    c->head_dim = c->hidden / c->heads;
+    if (c->hidden <= 0 || c->layers <= 0 || c->heads <= 0 || c->inter <= 0 || (!is_t5 && c->hidden % c->heads)) REJECT("missing or inconsistent backbone dimensions");
+    c->head_dim = is_t5 ? (int32_t)jnum(enc, "d_kv", 64) : c->hidden / c->heads;
     c->qk_norm = 0; c->attn_bias = 1;
     if (!strcmp(mt, "deberta-v2")) {
         c->backbone = GLC_BACKBONE_DEBERTA;
@@ -239,7 +242,26 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
         if (c->pad_id < 0) REJECT("pad_token_id %d is negative", c->pad_id);
         if (c->max_positions - c->pos_offset < 1) REJECT("max_position_embeddings %d leaves no position behind the offset %d", c->max_positions, c->pos_offset);
         if (c->type_vocab < 1) REJECT("type_vocab_size %d is not implemented (at least 1)", c->type_vocab);
-    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, qwen3, llama, modernbert, bert, roberta, xlm-roberta)", mt);
+    } else if (is_t5) {
+        /* transformers models/t5 (T5 v1.1, mT5, flan-T5 through T5EncoderModel): the encoder stack only */
+        c->backbone = GLC_BACKBONE_T5;
+        c->kv_heads = c->heads; c->causal = 0; c->rope_theta = 1.0e6f; c->global_every = 1; c->rope_theta_local = 1.0e4f;
+        c->pos_buckets = 0; c->max_rel_pos = 0;
+        c->ln_eps = (float)jnum(enc, "layer_norm_epsilon", 1e-6);
+        const char* ffp = jtext(enc, "feed_forward_proj");
+        if (!ffp) ffp = "relu";
+        if (strcmp(ffp, "gated-gelu")) REJECT("feed_forward_proj '%s' is not implemented (gated-gelu)", ffp);
+        const char* act = jtext(enc, "dense_act_fn");
+        if (act && strcmp(act, "gelu_new")) REJECT("dense_act_fn '%s' is not implemented (gelu_new)", act);
+        if (c->head_dim != 64) REJECT("d_kv %d is not implemented (64)", c->head_dim);
+        if (jflag(enc, "is_decoder", 0)) REJECT("is_decoder=true is not implemented");
+        c->rel_buckets = (int32_t)jnum(enc, "relative_attention_num_buckets", 32);
+        c->rel_max_distance = (int32_t)jnum(enc, "relative_attention_max_distance", 128);
+        if (c->rel_buckets < 4 || c->rel_buckets % 4 || c->rel_max_distance <= c->rel_buckets / 4)
+            REJECT("relative_attention_num_buckets %d / relative_attention_max_distance %d is not implemented (a multiple of 4, max distance beyond a quarter of it)",
+                   c->rel_buckets, c->rel_max_distance);
+        if (c->pad_id < 0) REJECT("pad_token_id %d is negative", c->pad_id);
+    } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, qwen3, llama, modernbert, bert, roberta, xlm-roberta, t5, mt5)", mt);
     return 0;
 }
 
@@ -335,8 +357,13 @@ int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
     glc_model_config* c = &w->cfg;
     char found[200];
     /* the embedding matrix decides the vocabulary size (tokens were added after the backbone config was written) */
-    const gj_value* emb = st_find(&st, c->backbone == GLC_BACKBONE_DECODER ? "embed_tokens.weight" :
+    const gj_value* emb = st_find(&st, c->backbone == GLC_BACKBONE_DECODER ? "embed_tokens.weight" : c->backbone == GLC_BACKBONE_T5 ? "shared.weight" :
                                        c->backbone == GLC_BACKBONE_MODERNBERT ? "embeddings.tok_embeddings.weight" : "embeddings.word_embeddings.weight", found, sizeof found);
+    const char* t5_emb = "shared.weight";                 /* (a bare T5EncoderModel may store the tied copy only) */
+    if (c->backbone == GLC_BACKBONE_T5 && !emb) { t5_emb = "encoder.embed_tokens.weight"; emb = st_find(&st, t5_emb, found, sizeof found); }
+    if (c->backbone == GLC_BACKBONE_T5 && !st_find(&st, "encoder.block.0.layer.0.SelfAttention.q.weight", found, sizeof found)) {
+        fprintf(stderr, "Error: '%s': is_encoder_decoder: the checkpoint holds no encoder tensors (encoder.block.0.layer.0.SelfAttention.q.weight)\n", stp); goto done;
+    }
     const gj_value* eshape = gj_get(emb, "shape");
     if (!emb || !gj_is(eshape, GJ_ARR) || eshape->u.arr.n != 2) { fprintf(stderr, "Error: '%s': no word-embedding tensor under any known prefix\n", stp); goto done; }
     c->vocab = (int32_t)eshape->u.arr.items[0]->u.num;
@@ -387,7 +414,28 @@ int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
             off += (n + 15) / 16 * 16;
             continue;
         }
-        if (st_read_f32(&st, stp, tn, nd, shp, w->_owned + off)) goto done;
+        /* T5: the fused Wqkv rows are the checkpoint's q | k | v, the fused Wgu rows its wi_0 | wi_1 */
+        const char* tq = c->backbone == GLC_BACKBONE_T5 ? strstr(tn, ".SelfAttention.Wqkv.") : NULL;
+        const char* tg = c->backbone == GLC_BACKBONE_T5 ? strstr(tn, ".DenseReluDense.Wgu.") : NULL;
+        if (tq || tg) {
+            static const char* const qkv[3] = {"q", "k", "v"};
+            static const char* const gu[2] = {"wi_0", "wi_1"};
+            const int np = tq ? 3 : 2;
+            const char* at = tq ? tq : tg;
+            const size_t skip = strlen(tq ? ".SelfAttention.Wqkv." : ".DenseReluDense.Wgu.");
+            int bad = 0;
+            for (int q = 0; q < np && !bad; ++q) {
+                char pn[160];
+                snprintf(pn, sizeof pn, "%.*s.%s.%s.%s", (int)(at - tn), tn, tq ? "SelfAttention" : "DenseReluDense", tq ? qkv[q] : gu[q], at + skip);
+                uint64_t pshp[2] = {shp[0] / (uint64_t)np, shp[1]};
+                if (st_read_f32(&st, stp, pn, nd, pshp, w->_owned + off + (size_t)q * (n / (size_t)np))) bad = 1;
+            }
+            if (bad) goto done;
+            w->tensors[i] = w->_owned + off;
+            off += (n + 15) / 16 * 16;
+            continue;
+        }
+        if (st_read_f32(&st, stp, (c->backbone == GLC_BACKBONE_T5 && i == 0) ? t5_emb : tn, nd, shp, w->_owned + off)) goto done;
         w->tensors[i] = w->_owned + off;
         off += (n + 15) / 16 * 16;
     }

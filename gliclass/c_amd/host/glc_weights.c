@@ -115,6 +115,24 @@ int glc_named_config(const char* name, glc_model_config* c) {
             c->max_positions = BT[i].maxpos; c->type_vocab = BT[i].types; c->pos_offset = BT[i].off;
             return 0;
         }
+    /* T5 v1.1 / mT5 backbones (config.py CONFIGS "t5-tiny", "t5-odd": 3 heads, inner width 192; "t5-mini"; "t5-base": the published v1.1 shape) */
+    static const struct { const char* n; int vocab, hidden, layers, heads, inter; } T5[] = {
+        {"t5-tiny", 515, 128, 2, 2, 256}, {"t5-odd", 515, 128, 2, 3, 256}, {"t5-mini", 1027, 256, 3, 4, 512}, {"t5-base", 32128, 768, 12, 12, 2048},
+    };
+    for (size_t i = 0; i < sizeof(T5) / sizeof(T5[0]); ++i)
+        if (strcmp(name, T5[i].n) == 0) {
+            memset(c, 0, sizeof(*c));
+            c->vocab = T5[i].vocab; c->hidden = T5[i].hidden; c->layers = T5[i].layers; c->heads = T5[i].heads;
+            c->head_dim = 64; c->inter = T5[i].inter; c->pos_buckets = 0; c->max_rel_pos = 0;
+            c->pad_id = 0; c->cls_id = 1; c->sep_id = 2;
+            c->class_token_index = c->vocab - 2; c->text_token_index = c->vocab - 1;
+            c->pooling = GLC_POOL_FIRST; c->scorer = GLC_SCORER_DOT; c->embed_class_token = 1; c->normalize_features = 0;
+            c->backbone = GLC_BACKBONE_T5; c->kv_heads = c->heads; c->causal = 0; c->rope_theta = 1.0e6f;
+            c->ln_eps = 1e-6f; c->logit_scale = 1.0f;
+            c->global_every = 1; c->rope_theta_local = 1.0e4f; c->attn_bias = 1;
+            c->rel_buckets = 32; c->rel_max_distance = 128;
+            return 0;
+        }
     return -1;
 }
 
@@ -223,6 +241,28 @@ int glc_tensor_spec(const glc_model_config* c, int i, char* name, uint64_t shape
             }
         }
         return head_spec(c, i - GLC_BERT_TENSORS_FIXED - nl, name, shape, amp, mean);
+    }
+    if (c->backbone == GLC_BACKBONE_T5) {               /* include/gliclass_hip.h; mirrors weights.tensor_specs */
+        char buf[96];
+        const uint64_t inner = (uint64_t)c->heads * (uint64_t)c->head_dim;
+        if (i == 0) SPEC2("shared.weight", (uint64_t)c->vocab, H, 1.0);
+        if (i == 1) SPEC2("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (uint64_t)c->rel_buckets, (uint64_t)c->heads, 3.0);
+        const int nl = GLC_T5_TENSORS_PER_LAYER * c->layers;
+        if (i >= GLC_T5_TENSORS_FIXED && i < GLC_T5_TENSORS_FIXED + nl) {
+            const int l = (i - GLC_T5_TENSORS_FIXED) / GLC_T5_TENSORS_PER_LAYER, k = (i - GLC_T5_TENSORS_FIXED) % GLC_T5_TENSORS_PER_LAYER;
+            static const char* sfx[6] = {"layer.0.layer_norm.weight", "layer.0.SelfAttention.Wqkv.weight", "layer.0.SelfAttention.o.weight",
+                                         "layer.1.layer_norm.weight", "layer.1.DenseReluDense.Wgu.weight", "layer.1.DenseReluDense.wo.weight"};
+            snprintf(buf, sizeof buf, "encoder.block.%d.%s", l, sfx[k]);
+            switch (k) {
+                case 0: case 3: SPEC1(buf, H, 0.2, 1.0);
+                case 1: SPEC2(buf, 3 * inner, H, lin_amp(0.6, (double)H));
+                case 2: SPEC2(buf, H, inner, lin_amp(1.0, (double)inner));
+                case 4: SPEC2(buf, 2 * I, H, lin_amp(1.0, (double)H));
+                default: SPEC2(buf, H, I, lin_amp(0.7, (double)I));
+            }
+        }
+        if (i == GLC_T5_TENSORS_FIXED + nl) SPEC1("encoder.final_layer_norm.weight", H, 0.2, 1.0);
+        return head_spec(c, i - GLC_T5_TENSORS_FIXED - nl - 1, name, shape, amp, mean);
     }
     if (c->backbone == GLC_BACKBONE_DECODER) {
         const uint64_t nqd = (uint64_t)c->heads * (uint64_t)c->head_dim;
@@ -368,7 +408,8 @@ static int load_blob(const char* path, glc_weights* w) {
     c->ln_eps = fl[0]; c->logit_scale = fl[1]; c->rope_theta = fl[2];
     c->qk_norm = 0; c->attn_bias = 1;         /* what every blob older than version 4 means */
     c->max_positions = 0; c->type_vocab = 0; c->pos_offset = 0;      /* ... and every blob older than version 5 */
-    if (ver >= 3 && ver <= 5) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
+    c->rel_buckets = 0; c->rel_max_distance = 0;                     /* ... and every blob older than version 6 */
+    if (ver >= 3 && ver <= 6) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
         int32_t i3[2];
         float f3;
         memcpy(i3, b + 16 + sizeof ints + sizeof fl, sizeof i3);
@@ -378,17 +419,25 @@ static int load_blob(const char* path, glc_weights* w) {
             int32_t i4[2];
             memcpy(i4, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3, sizeof i4);
             c->qk_norm = i4[0]; c->attn_bias = i4[1];
-            if (ver == 5) {  /* written for the BERT backbone only: + max_positions, type_vocab, pos_offset */
+            if (ver >= 5) {  /* written for the BERT backbone only: + max_positions, type_vocab, pos_offset */
                 int32_t i5[3];
                 memcpy(i5, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3 + sizeof i4, sizeof i5);
                 c->max_positions = i5[0]; c->type_vocab = i5[1]; c->pos_offset = i5[2];
+                if (ver == 6) {  /* written for the T5 backbone only: + rel_buckets, rel_max_distance */
+                    int32_t i6[2];
+                    memcpy(i6, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3 + sizeof i4 + sizeof i5, sizeof i6);
+                    c->rel_buckets = i6[0]; c->rel_max_distance = i6[1];
+                }
             }
         }
     }
     const int bert_bad = (c->backbone == GLC_BACKBONE_BERT) != (ver == 5) ||
                          (ver == 5 && (c->max_positions < 1 || c->max_positions > (1 << 24) || c->type_vocab < 1 || c->type_vocab > (1 << 16) ||
                                        c->pos_offset < 0 || c->max_positions - c->pos_offset < 1));
-    if (ver < 2 || ver > 5 || bert_bad || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
+    const int t5_bad = (c->backbone == GLC_BACKBONE_T5) != (ver == 6) ||
+                       (ver == 6 && (c->rel_buckets < 4 || c->rel_buckets % 4 || c->rel_buckets > (1 << 16) || c->rel_max_distance <= c->rel_buckets / 4 ||
+                                     c->heads < 1 || c->heads > (1 << 12)));
+    if (ver < 2 || ver > 6 || bert_bad || t5_bad || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
         fprintf(stderr, "Error: '%s': unsupported GLCW header (version %u, %u tensors)\n", path, ver, nt);
         return -1;
     }

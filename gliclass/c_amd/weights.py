@@ -16,7 +16,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from .config import GLiClassConfig, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
+from .config import GLiClassConfig, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, BACKBONE_T5, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
 from . import prng
 
 MAGIC = b"GLCW\x00\x01\x00\x00"
@@ -34,6 +34,8 @@ _V3_F32_FIELDS = ["rope_theta_local"]
 _V4_INT_FIELDS = ["qk_norm", "attn_bias"]
 # version 5 (BERT backbone only): + max_positions, type_vocab, pos_offset (int32) after the v4 slots
 _V5_INT_FIELDS = ["max_positions", "type_vocab", "pos_offset"]
+# version 6 (T5 backbone only): + rel_buckets, rel_max_distance (int32) after the v5 slots
+_V6_INT_FIELDS = ["rel_buckets", "rel_max_distance"]
 
 
 def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float, float]]:
@@ -122,6 +124,26 @@ def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float,
             ]
         return specs + head_specs()
 
+    if cfg.backbone == BACKBONE_T5:
+        # HF T5EncoderModel.state_dict() names, with q / k / v fused into Wqkv (rows q | k | v) and wi_0 / wi_1 into Wgu (rows wi_0 | wi_1):
+        # from_state_dict and the C importer concatenate them.  T5 does not scale its scores, so q and k are drawn narrow enough for a
+        # score spread of 2-3 (0.6^2 * sqrt(64)); the bias table spreads over a few units, so that a skipped bias is visible.
+        inner = cfg.heads * cfg.head_dim
+        specs = [("shared.weight", (cfg.vocab, H), 1.0, 0.0),
+                 ("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", (cfg.rel_buckets, cfg.heads), 3.0, 0.0)]
+        for i in range(L):
+            p = f"encoder.block.{i}."
+            specs += [
+                (p + "layer.0.layer_norm.weight", (H,), 0.2, 1.0),
+                (p + "layer.0.SelfAttention.Wqkv.weight", (3 * inner, H), lin(0.6, H), 0.0),
+                (p + "layer.0.SelfAttention.o.weight", (H, inner), lin(1.0, inner), 0.0),
+                (p + "layer.1.layer_norm.weight", (H,), 0.2, 1.0),
+                (p + "layer.1.DenseReluDense.Wgu.weight", (2 * I, H), lin(1.0, H), 0.0),
+                (p + "layer.1.DenseReluDense.wo.weight", (H, I), lin(0.7, I), 0.0),
+            ]
+        specs += [("encoder.final_layer_norm.weight", (H,), 0.2, 1.0)]
+        return specs + head_specs()
+
     if cfg.backbone == BACKBONE_DECODER:
         # HF Qwen2Model / LlamaModel / Qwen3Model.state_dict() names (prefix-free).  q/k amplitudes give score std ~ 2-3 after 1/sqrt(d).
         # Qwen3's q_norm / k_norm gains: drawn around 1 like the other norm gains, with a wider spread and another centre for q (1.1 +- 0.4)
@@ -188,10 +210,11 @@ def make_weights(cfg: GLiClassConfig, seed: int = 42) -> Dict[str, np.ndarray]:
 
 def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
     d = cfg.asdict()
-    v5 = cfg.backbone == BACKBONE_BERT                # v5 carries the v3 and v4 slots too
+    v6 = cfg.backbone == BACKBONE_T5                  # v6 carries the v3, v4 and v5 slots too
+    v5 = v6 or cfg.backbone == BACKBONE_BERT          # v5 carries the v3 and v4 slots too
     v4 = v5 or (cfg.qk_norm, cfg.attn_bias) != (0, 1)       # Llama / Qwen3 decoders; v4 carries the v3 slots too
     v3 = cfg.backbone == BACKBONE_MODERNBERT          # every other backbone keeps writing byte-identical v2 headers
-    b = MAGIC + struct.pack("<II", 5 if v5 else 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
+    b = MAGIC + struct.pack("<II", 6 if v6 else 5 if v5 else 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
     b += struct.pack("<%di" % len(_INT_FIELDS), *[int(d[k]) for k in _INT_FIELDS])
     b += struct.pack("<%df" % len(_F32_FIELDS), *[float(d[k]) for k in _F32_FIELDS])
     if v3 or v4:
@@ -201,6 +224,8 @@ def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
         b += struct.pack("<%di" % len(_V4_INT_FIELDS), *[int(d[k]) for k in _V4_INT_FIELDS])
     if v5:
         b += struct.pack("<%di" % len(_V5_INT_FIELDS), *[int(d[k]) for k in _V5_INT_FIELDS])
+    if v6:
+        b += struct.pack("<%di" % len(_V6_INT_FIELDS), *[int(d[k]) for k in _V6_INT_FIELDS])
     assert len(b) <= HEADER_BYTES
     return b + b"\x00" * (HEADER_BYTES - len(b))
 
@@ -238,7 +263,7 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if hdr[:8] != MAGIC:
         raise ValueError("not a GLCW blob")
     ver, n_t = struct.unpack_from("<II", hdr, 8)
-    if ver not in (2, 3, 4, 5):
+    if ver not in (2, 3, 4, 5, 6):
         raise ValueError(f"unsupported GLCW version {ver}")
     ints = struct.unpack_from("<%di" % len(_INT_FIELDS), hdr, 16)
     flts = struct.unpack_from("<%df" % len(_F32_FIELDS), hdr, 16 + 4 * len(_INT_FIELDS))
@@ -254,6 +279,9 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if ver >= 5:
         o5 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS) + len(_V4_INT_FIELDS))
         kw.update(dict(zip(_V5_INT_FIELDS, struct.unpack_from("<%di" % len(_V5_INT_FIELDS), hdr, o5))))
+    if ver >= 6:
+        o6 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS) + len(_V4_INT_FIELDS) + len(_V5_INT_FIELDS))
+        kw.update(dict(zip(_V6_INT_FIELDS, struct.unpack_from("<%di" % len(_V6_INT_FIELDS), hdr, o6))))
     cfg = GLiClassConfig(name="blob", **kw)
     tensors = {}
     for i in range(n_t):
@@ -274,7 +302,7 @@ def from_state_dict(sd: Dict[str, "np.ndarray"], cfg: GLiClassConfig, names=None
     out = {}
     want = [s[0] for s in tensor_specs(cfg)] if names is None else list(names)
     prefixes = ("", "deberta.", "encoder_model.model.", "model.encoder_model.model.", "model.", "decoder_model.model.") + \
-        (_BERT_PREFIXES if cfg.backbone == BACKBONE_BERT else ())
+        (_BERT_PREFIXES if cfg.backbone in (BACKBONE_BERT, BACKBONE_T5) else ())
 
     def find(n):
         for pre in prefixes:
@@ -286,6 +314,15 @@ def from_state_dict(sd: Dict[str, "np.ndarray"], cfg: GLiClassConfig, names=None
     for n in want:
         if cfg.backbone == BACKBONE_BERT and ".attention.self.Wqkv." in n:      # HF keeps query / key / value apart: rows Q | K | V
             out[n] = np.concatenate([find(n.replace("Wqkv", part)) for part in ("query", "key", "value")], axis=0)
+        elif cfg.backbone == BACKBONE_T5 and ".SelfAttention.Wqkv." in n:       # T5Attention q / k / v: rows q | k | v
+            out[n] = np.concatenate([find(n.replace("Wqkv", part)) for part in ("q", "k", "v")], axis=0)
+        elif cfg.backbone == BACKBONE_T5 and ".DenseReluDense.Wgu." in n:       # T5DenseGatedActDense wi_0 / wi_1: rows wi_0 | wi_1
+            out[n] = np.concatenate([find(n.replace("Wgu", part)) for part in ("wi_0", "wi_1")], axis=0)
+        elif cfg.backbone == BACKBONE_T5 and n == "shared.weight":              # (a bare T5EncoderModel may store the tied copy only)
+            try:
+                out[n] = find(n)
+            except KeyError:
+                out[n] = find("encoder.embed_tokens.weight")
         else:
             out[n] = find(n)
     return out
@@ -348,4 +385,67 @@ def load_bert_checkpoint(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarra
     if not emb:
         raise KeyError("embeddings.word_embeddings.weight")
     cfg = bert_config_from_hf(root, vocab=emb[0].shape[0])
+    return cfg, from_state_dict(sd, cfg)
+
+
+# ---- T5 / mT5 checkpoints (mirrors parse_config of host/glc_safetensors.c) ----
+T5_MODEL_TYPES = ("t5", "mt5")
+
+
+def t5_config_from_hf(root: dict, vocab: int = None) -> GLiClassConfig:
+    """GLiClassConfig of a T5-family checkpoint's config.json (`root`; the backbone's own fields under encoder_config, or a bare
+    backbone config).  `vocab` = rows of the shared embedding.  Everything the engine does not build is refused with a message that
+    names the field."""
+    from .config import SCORER_NAMES, POOL_FIRST, POOL_AVG, POOL_LAST
+    enc = root.get("encoder_config") if isinstance(root.get("encoder_config"), dict) else root
+    mt = enc.get("model_type")
+    if mt == "umt5":
+        raise ValueError("model_type 'umt5' is not implemented (a relative_attention_bias table per layer; t5 and mt5 share layer 0's)")
+    if mt not in T5_MODEL_TYPES:
+        raise ValueError(f"backbone model_type '{mt}' is not a T5-family type (t5, mt5)")
+    ffp = enc.get("feed_forward_proj", "relu")
+    if ffp != "gated-gelu":
+        raise ValueError(f"feed_forward_proj '{ffp}' is not implemented (gated-gelu)")
+    act = enc.get("dense_act_fn", "gelu_new")
+    if act != "gelu_new":
+        raise ValueError(f"dense_act_fn '{act}' is not implemented (gelu_new)")
+    dkv = int(enc.get("d_kv", 64))
+    if dkv != 64:
+        raise ValueError(f"d_kv {dkv} is not implemented (64)")
+    if enc.get("is_decoder", False):
+        raise ValueError("is_decoder=true is not implemented")
+    nb, md = int(enc.get("relative_attention_num_buckets", 32)), int(enc.get("relative_attention_max_distance", 128))
+    if nb < 4 or nb % 4 or md <= nb // 4:
+        raise ValueError(f"relative_attention_num_buckets {nb} / relative_attention_max_distance {md} is not implemented "
+                         "(a multiple of 4, max distance beyond a quarter of it)")
+    pool = {"first": POOL_FIRST, "avg": POOL_AVG, "last": POOL_LAST}[root.get("pooling_strategy", "first")]
+    vocab = int(vocab if vocab is not None else root.get("vocab_size", enc.get("vocab_size")))
+    return GLiClassConfig(
+        name="checkpoint", vocab=vocab, hidden=int(enc["d_model"]), layers=int(enc["num_layers"]), heads=int(enc["num_heads"]),
+        inter=int(enc["d_ff"]), head_dim=64, pos_buckets=0, max_rel_pos=0, ln_eps=float(enc.get("layer_norm_epsilon", 1e-6)),
+        pad_id=int(enc.get("pad_token_id", 0)), cls_id=int(enc.get("cls_token_id", enc.get("bos_token_id", 1)) or 1),
+        sep_id=int(enc.get("sep_token_id", enc.get("eos_token_id", 2))),
+        class_token_index=int(root.get("class_token_index", -1)), text_token_index=int(root.get("text_token_index", -1)), pooling=pool,
+        scorer=SCORER_NAMES[root.get("scorer_type", "simple")], embed_class_token=int(bool(root.get("embed_class_token", True))),
+        normalize_features=int(bool(root.get("normalize_features", False))), logit_scale=float(root.get("logit_scale", 1.0)),
+        backbone=BACKBONE_T5, causal=0, rel_buckets=nb, rel_max_distance=md)
+
+
+def load_t5_checkpoint(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
+    """An HF directory (config.json + model.safetensors) of a T5-family backbone -> (config, tensors in blob order).  Decoder-side
+    tensors are ignored; a checkpoint without encoder tensors is refused."""
+    import json
+    import os
+    from safetensors.numpy import load_file
+    with open(os.path.join(path, "config.json")) as f:
+        root = json.load(f)
+    cfg0 = t5_config_from_hf(root, vocab=1)                   # (the refusals, before the file is read)
+    sd = load_file(os.path.join(path, "model.safetensors"))
+    if not any(k.endswith("encoder.block.0.layer.0.SelfAttention.q.weight") for k in sd):
+        raise ValueError("is_encoder_decoder: the checkpoint holds no encoder tensors (encoder.block.0.layer.0.SelfAttention.q.weight)")
+    emb = [v for k, v in sd.items() if k.endswith("shared.weight") or k.endswith("encoder.embed_tokens.weight")]
+    if not emb:
+        raise KeyError("shared.weight")
+    cfg = t5_config_from_hf(root, vocab=emb[0].shape[0])
+    del cfg0
     return cfg, from_state_dict(sd, cfg)

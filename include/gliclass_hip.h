@@ -42,7 +42,11 @@ enum { GLC_BACKBONE_DEBERTA = 0, GLC_BACKBONE_DECODER = 1,
                                       local layers, GeGLU (transformers models/modernbert/modeling_modernbert.py) */,
        GLC_BACKBONE_BERT = 3 /* BERT / RoBERTa / XLM-R encoder: learned absolute position embeddings (+ token-type row 0), post-LayerNorm blocks
                                 with biases, plain bidirectional attention, erf-GELU FFN (transformers models/bert/modeling_bert.py,
-                                models/roberta/modeling_roberta.py) */ };
+                                models/roberta/modeling_roberta.py) */,
+       GLC_BACKBONE_T5 = 4 /* T5 v1.1 / mT5 / flan-T5 encoder (transformers models/t5/modeling_t5.py, the encoder T5Stack): pre-norm blocks on
+                              bias-free RMSNorms and projections, attention without the 1/sqrt(d) scale and with a learned per-head bias
+                              indexed by the bucket of key - query (layer 0's table, shared by every layer), gated tanh-GELU FFN; heads *
+                              head_dim need not be the hidden size */ };
 
 /* Same int/float slots, same order, as the .glcw blob header (gliclass/c_amd/weights.py). */
 typedef struct glc_model_config {
@@ -63,6 +67,9 @@ typedef struct glc_model_config {
      * 0 .. S-1 (BERT), pos_offset = pad_id + 1 numbers the non-pad tokens from pos_offset on and gives pad tokens row pad_id (RoBERTa / XLM-R,
      * create_position_ids_from_input_ids).  A forward takes at most max_positions - pos_offset tokens per row.  0 on every other backbone. */
     int32_t max_positions, type_vocab, pos_offset;
+    /* T5 backbone: relative_attention_num_buckets and relative_attention_max_distance of the bias table (bidirectional buckets).  0 on every
+     * other backbone. */
+    int32_t rel_buckets, rel_max_distance;
 } glc_model_config;
 
 /* Tensor order expected in `tensors[]` (all fp32, row-major, nn.Linear weights are [out,in]):
@@ -106,7 +113,17 @@ static inline int glc_dec_tensors_per_layer(const glc_model_config* c) { return 
  *   then the same 8 head tensors */
 #define GLC_BERT_TENSORS_FIXED 5
 #define GLC_BERT_TENSORS_PER_LAYER 12
+/* T5 backbone (names of HF T5EncoderModel.state_dict() except the fused attention projection; no biases anywhere; inner = heads * head_dim):
+ *   0 shared.weight [vocab,H]      1 encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight [rel_buckets,heads]
+ *   2+6*l .. : block l: layer.0.layer_norm.weight [H]  layer.0.SelfAttention.Wqkv.weight [3*inner,H] (rows: q | k | v, concatenated by the importers)
+ *                       layer.0.SelfAttention.o.weight [H,inner]  layer.1.layer_norm.weight [H]
+ *                       layer.1.DenseReluDense.Wgu.weight [2I,H] (rows: wi_0 | wi_1, concatenated by the importers)  layer.1.DenseReluDense.wo.weight [H,I]
+ *   then encoder.final_layer_norm.weight [H], then the same 8 head tensors */
+#define GLC_T5_TENSORS_FIXED 2
+#define GLC_T5_TENSORS_PER_LAYER 6
 static inline int glc_num_tensors_cfg(const glc_model_config* c) {
+    if (c->backbone == GLC_BACKBONE_T5)
+        return GLC_T5_TENSORS_FIXED + GLC_T5_TENSORS_PER_LAYER * c->layers + 1 + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     if (c->backbone == GLC_BACKBONE_BERT)
         return GLC_BERT_TENSORS_FIXED + GLC_BERT_TENSORS_PER_LAYER * c->layers + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     if (c->backbone == GLC_BACKBONE_MODERNBERT)
@@ -163,8 +180,8 @@ int glc_engine_device_forward_valid(glc_engine* e);      /* 1 valid / 0 repeat t
  * inter % 32 == 0 (modernbert-large, 2 x 2624 = 5248, is not eligible); head_dim 64; not under glc_debug_keep_hidden.  The activation
  * exponent is chosen here from the LayerNorm gains (max |gamma| sqrt(hidden) > 448: exponent -5 from the start).  Afterwards GLICLASS_MX=build,
  * glc_debug_set_mx, glc_debug_set_mx_attention, the glc_debug_last_forward_mx* queries and the fp8 range guard behave as on the decoder
- * backbone.  On the other backbones: 0 if the MX pipeline is available to the engine, else -1; nothing changes (the BERT backbone has no MX
- * pipeline: always -1, the message says so).
+ * backbone.  On the other backbones: 0 if the MX pipeline is available to the engine, else -1; nothing changes (the BERT and T5 backbones
+ * have no MX pipeline: always -1, the message says so).
  * Environment: GLICLASS_MX_MODERNBERT=1, read once in glc_engine_create, makes this call for a ModernBERT engine (a failure leaves the
  * engine as it is and is not an error). */
 int glc_engine_enable_mx(glc_engine* e);
@@ -204,7 +221,7 @@ int glc_debug_graph_cache_size(const glc_engine* e);       /* graph executables 
  * arithmetic's ~4e-5 — the error large forwards have by default; that is why it is opt-in.  The fp8 range guard, its retries and
  * glc_engine_sync's report apply unchanged.  Speed: not measured yet; nothing is promised.
  * Changing the mode drops every cached graph.  Returns 0; -1 (glc_last_error) for a null engine, a mode outside 0 .. 2, or mode >= 1 on the
- * decoder / ModernBERT / BERT backbones (the message names the backbone; mode 0 returns 0 there).
+ * decoder / ModernBERT / BERT / T5 backbones (the message names the backbone; mode 0 returns 0 there).
  * Environment: GLICLASS_MX_SMALL=1|2, read once in glc_engine_create, makes this call (a failure leaves the engine as it is, not an error). */
 int glc_engine_set_mx_small_forwards(glc_engine* e, int mode);
 int glc_debug_last_forward_mx128(const glc_engine* e);     /* GEMM launches of the last forward that ran on the 128 tile (0: none); -1: null engine */
@@ -295,6 +312,10 @@ int glc_debug_set_gemm_full_lines(int on);
 /* clamp(bucket(q-k)+span, 0, 2span-1) for q-k in [-(S-1), S-1] at out[q-k+S-1] (float32 math as
  * torch).  Pure host function (no GPU needed). */
 void glc_delta_table(int S, int bucket_size, int max_position, int32_t* out);
+/* T5 backbone: T5Attention._relative_position_bucket (bidirectional) of delta = key - query for delta in [-(S-1), S-1] at out[delta + S - 1]:
+ * half the buckets for delta > 0, distances below num_buckets / 4 exact, beyond them float32 log spacing up to max_distance, truncated and
+ * clamped (float32 math as torch).  Pure host function (no GPU needed). */
+void glc_t5_bucket_table(int S, int num_buckets, int max_distance, int32_t* out);
 
 /* Developer microbenchmark of one GEMM shape (16-bit engines): ms per launch, <0 on error. */
 float glc_debug_gemm_bench(glc_engine* e, int M, int N, int K, int epi, int iters, int which);
