@@ -23,7 +23,8 @@ class ModelConfig(C.Structure):
                 ("local_window", C.c_int32), ("global_every", C.c_int32), ("rope_theta_local", C.c_float),
                 ("qk_norm", C.c_int32), ("attn_bias", C.c_int32),
                 ("max_positions", C.c_int32), ("type_vocab", C.c_int32), ("pos_offset", C.c_int32),
-                 ("rel_buckets", C.c_int32), ("rel_max_distance", C.c_int32)]
+                 ("rel_buckets", C.c_int32), ("rel_max_distance", C.c_int32),
+                ("head_kind", C.c_int32), ("cls_labels", C.c_int32), ("cls_act", C.c_int32), ("cls_norm", C.c_int32), ("cls_dense", C.c_int32)]
 
 
 class Weights(C.Structure):
@@ -63,7 +64,8 @@ HIP_SYMBOLS = ["glc_device_count", "glc_last_error", "glc_engine_create", "glc_e
                "glc_debug_keep_hidden", "glc_debug_get_hidden", "glc_debug_set_attention_impl", "glc_delta_table", "glc_debug_last_forward_pruned",
                "glc_engine_config", "glc_engine_dtype", "glc_debug_gemm_bench", "glc_debug_attn_bench", "glc_engine_set_prune_last_layer", "glc_engine_set_length_buckets", "glc_plan_length_buckets", "glc_debug_last_forward_groups", "glc_debug_set_group_split", "glc_debug_last_forward_group_split", "glc_debug_set_ln_fused", "glc_debug_last_forward_ln_folded", "glc_debug_set_precision_mask", "glc_debug_set_gemm_full_lines", "glc_debug_range_retries", "glc_debug_fp8_range_retries", "glc_debug_fp8_range_sticky", "glc_debug_activation_exponent", "glc_debug_is_developer_build", "glc_engine_device_forward_valid", "glc_debug_mx_weight_bytes", "glc_debug_set_mx", "glc_debug_last_forward_mx", "glc_debug_last_forward_mx_attention", "glc_debug_set_stop", "glc_debug_read_workspace", "glc_debug_set_mx_attention", "glc_debug_gemm_run", "glc_debug_ln_stats_run", "glc_debug_last_forward_rope_epilogue", "glc_engine_enable_mx",
                "glc_engine_set_graph_replay", "glc_debug_last_forward_graph", "glc_debug_graph_cache_size",
-               "glc_engine_set_mx_small_forwards", "glc_debug_last_forward_mx128", "glc_debug_read_pos_ids", "glc_t5_bucket_table"]
+               "glc_engine_set_mx_small_forwards", "glc_debug_last_forward_mx128", "glc_debug_read_pos_ids", "glc_t5_bucket_table",
+               "glc_engine_nli_scores"]
 MODEL_SYMBOLS = ["flatten_int_array", "create_tensor", "prepare_input_tensors", "initialize_ort_api",
                  "initialize_ort_environment", "create_ort_session", "run_inference", "parallel_inference",
                  "glc_session_num_devices", "parallel_preprocess", "parallel_postprocess", "sigmoid",
@@ -139,6 +141,7 @@ def hip():
         L.glc_debug_read_pos_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.glc_t5_bucket_table.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.glc_t5_bucket_table.restype = None
+        L.glc_engine_nli_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.glc_debug_last_forward_mx_attention.argtypes = [C.c_void_p]
         L.glc_debug_last_forward_rope_epilogue.argtypes = [C.c_void_p]
         L.glc_debug_set_stop.argtypes = [C.c_void_p, C.c_int]

@@ -16,6 +16,9 @@ SCORER_MLP = 2
 SCORER_MLP_HIDDEN = 256
 SCORER_NAMES = {"simple": SCORER_DOT, "weighted-dot": SCORER_WEIGHTED_DOT, "mlp": SCORER_MLP}
 BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, BACKBONE_T5 = 0, 1, 2, 3, 4
+HEAD_GLICLASS, HEAD_SEQCLS = 0, 1
+CLS_ACT_NONE, CLS_ACT_TANH, CLS_ACT_GELU = 0, 1, 2
+CLS_MAX_LABELS = 1024
 
 
 @dataclass(frozen=True)
@@ -67,8 +70,21 @@ class GLiClassConfig:
     # `hidden` (mt5-small: 6 x 64 on 512); ln_eps is layer_norm_epsilon, `inter` d_ff (the gated-gelu width)
     rel_buckets: int = 0
     rel_max_distance: int = 0
+    # head_kind = HEAD_SEQCLS: the head of an HF *ForSequenceClassification checkpoint in place of the GLiClass head (DeBERTa, BERT / RoBERTa /
+    # XLM-R and ModernBERT backbones): pooled row (`pooling` first / avg) -> [dense H x H] -> cls_act (0 none, 1 tanh, 2 erf-GELU) ->
+    # [LayerNorm, epsilon ln_eps] -> classifier with cls_labels outputs.  All 0 with the GLiClass head.
+    head_kind: int = HEAD_GLICLASS
+    cls_labels: int = 0
+    cls_act: int = CLS_ACT_NONE
+    cls_norm: int = 0
+    cls_dense: int = 0
 
     def __post_init__(self):
+        if self.head_kind == HEAD_SEQCLS:
+            assert 1 <= self.cls_labels <= CLS_MAX_LABELS and self.cls_act in (0, 1, 2) and self.cls_norm in (0, 1) and self.cls_dense in (0, 1)
+            assert self.pooling in (POOL_FIRST, POOL_AVG)
+        else:
+            assert self.head_kind == HEAD_GLICLASS and (self.cls_labels, self.cls_act, self.cls_norm, self.cls_dense) == (0, 0, 0, 0)
         # (a decoder checkpoint names its head_dim: Qwen3's is not hidden / heads; T5's inner width is num_heads * d_kv)
         assert self.backbone in (BACKBONE_DECODER, BACKBONE_T5) or self.hidden == self.heads * self.head_dim
         assert self.qk_norm in (0, 1) and self.attn_bias in (0, 1) and (self.backbone == BACKBONE_DECODER or self.qk_norm == 0)

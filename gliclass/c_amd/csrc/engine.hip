@@ -268,7 +268,8 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
         if (!regrow(e, e->d_ids, (size_t)B * S * sizeof(int64_t)) || !regrow(e, e->d_mask, (size_t)B * S * sizeof(int64_t))) return false;
         e->capIds = B * S;
     }
-    const int hr = round_up(B, 128) + round_up(B * (C > 0 ? C : 1), 128);      // text rows then class rows, each group 128-aligned
+    const bool seqcls = c.head_kind == GLC_HEAD_SEQCLS;      // (its C is the label count: no class rows, neither in the head nor in the pruned last layer)
+    const int hr = round_up(B, 128) + (seqcls ? 0 : round_up(B * (C > 0 ? C : 1), 128));      // text rows then class rows, each group 128-aligned
     if (hr > e->capHeadRows) {
         for (float** b : {&e->Gt, &e->G1t, &e->G2t}) if (!regrow(e, *b, (size_t)hr * c.hidden * sizeof(float))) return false;
         // weighted-dot: [hr, 2H] + [rc, 3H] + [rc, 4H]; mlp: [rc, 2H] + [rc, 256] + [rc, 128] (rc <= hr)
@@ -277,7 +278,7 @@ bool ensure_capacity(glc_engine* e, int B, int S, int C) {
     }
     // compact rows of the pruned last layer (every backbone): R = B (1 + C) rows up to the 256-row grid of the small-M GEMMs; the decoder's
     // context rows are heads * head_dim wide, which need not be the hidden size
-    const int rsel = round_up(B * (1 + (C > 0 ? C : 0)), 256);
+    const int rsel = round_up(B * (1 + (C > 0 && !seqcls ? C : 0)), 256);
     if (rsel > e->capSel && !bert) {       // (BERT: no pruned last layer)
         const size_t wide = dec ? std::max((size_t)c.hidden, (size_t)nh_ws * c.head_dim) : (size_t)c.hidden;
         for (void** b : {&e->Xs, &e->CTXs, &e->T1s, &e->H1s}) if (!regrow(e, *b, (size_t)rsel * wide * es)) return false;
@@ -479,6 +480,26 @@ bool run_head_tail(glc_engine* e, int B, int C, float* d_logits) {
 }
 
 inline int class_cap(const glc_engine* e) { return e->capC > 0 ? e->capC : 1; }
+// class-token rows per text that the head reads (the pruned last layers keep them): none for the sequence-classification head, whose C counts labels
+inline int class_rows(const glc_engine* e, int C) { return e->cfg.head_kind == GLC_HEAD_SEQCLS || C < 0 ? 0 : C; }
+
+// The sequence-classification head on the B pooled rows in Gt (cls_head.hip has the arithmetic and its sources): the dense stage on the GEMM path
+// of the GLiClass projectors (fp32 rows, split-f16 weights), then activation, norm, classifier and bias in one launch -> logits [B, K]
+bool run_cls_head(glc_engine* e, int B, float* d_logits) {
+    const glc_model_config& c = e->cfg;
+    const int H = c.hidden;
+    const float* x = e->Gt;
+    if (c.cls_dense) {
+        GemmArgs h;
+        h.N = H; h.K = H; h.Mpad = round_up(B, 128);
+        h.A = e->Gt; h.W = e->clsw[0]; h.bias = e->clsw[1]; h.C = e->G1t;
+        KCHK(launch_gemm128(e, GLC_F32, EPI_BIAS, h), false);
+        x = e->G1t;
+    }
+    KCHK(glc_launch_cls_head(e->stream, x, c.cls_norm ? e->clsw[2] : nullptr, c.cls_norm ? e->clsw[3] : nullptr, e->clsw[4], e->clsw[5], d_logits,
+                             B, H, c.cls_labels, c.cls_act, c.ln_eps), false);
+    return true;
+}
 
 // The start of every forward: profiler reset, the hidden-state dump buffer (keep_hidden: L + 1 slots of M rows), scan_rows.
 bool forward_prologue(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S) {
@@ -507,7 +528,13 @@ bool forward_epilogue(glc_engine* e, const void* rows, bool compact, int B, int 
     const glc_model_config& c = e->cfg;
     const int H = c.hidden, Sp = round_up(S, 64), dt = e->dtype;
     hipStream_t st = e->stream;
-    if (C > 0) {
+    if (c.head_kind == GLC_HEAD_SEQCLS) {      // pooled rows only (compact rows: row b is text b's), then the classifier; C = cls_labels (checked by the entries)
+        Prof p(e, PC_HEAD);
+        if (compact) KCHK(glc_launch_head_gather_sel(st, dt, rows, e->cls_pos, class_cap(e), e->Gt, e->Gt, B, H, 0), false);
+        else if (c.pooling == GLC_POOL_AVG) KCHK(glc_launch_pool_avg(st, dt, rows, e->kbias, e->Gt, B, Sp, H), false);
+        else KCHK(glc_launch_head_gather(st, dt, rows, e->cls_pos, class_cap(e), e->Gt, e->Gt, B, Sp, H, 0, nullptr), false);
+        if (!run_cls_head(e, B, d_logits)) return false;
+    } else if (C > 0) {
         Prof p(e, PC_HEAD);
         float* Gc = e->Gt + (size_t)round_up(B, 128) * H;
         if (compact) KCHK(glc_launch_head_gather_sel(st, dt, rows, e->cls_pos, class_cap(e), e->Gt, Gc, B, H, C), false);
@@ -586,7 +613,7 @@ PrunedTail pruned_tail(const glc_engine* e, int B, int C) {
     PrunedTail t;
     const glc_model_config& c = e->cfg;
     t.on = e->prune_last && !e->keep_hidden && (c.pooling == GLC_POOL_FIRST || c.pooling == GLC_POOL_LAST) && c.layers > 0;
-    t.Cc = C > 0 ? C : 0;
+    t.Cc = class_rows(e, C);
     t.R = B * (1 + t.Cc); t.Rpad = round_up(t.R, 256);
     t.klen = c.pooling == GLC_POOL_LAST ? e->klen : nullptr;
     return t;
@@ -1113,7 +1140,7 @@ bool run_forward_deberta(glc_engine* e, const int64_t* ids, const int64_t* mask,
         if (e->debug_stop == 10 * l + 4) return true;
         if (!dump_hidden(e, l + 1, e->X, M)) return false;
     }
-    const int Cc = C > 0 ? C : 0;
+    const int Cc = class_rows(e, C);
     if (prune) {
         // Last layer, exact pruning: the head reads only the [CLS] row and the class-token rows, so only those
         // R = B*(1+C) rows need Q, attention output, the output projection and the FFN.  K and V^T are still
@@ -1187,7 +1214,7 @@ bool run_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, 
 // addresses the key pins.  H2D / D2H copies of the host-buffer entry, the range guard's counter read and every host decision stay outside.
 GraphKey graph_key(const glc_engine* e, const void* ids, const void* mask, int B, int S, int C, const void* d_logits) {
     GraphKey k;
-    k.backbone = e->cfg.backbone; k.B = B; k.S = S; k.Sp = round_up(S, 64); k.C = C;
+    k.backbone = e->cfg.backbone; k.head = e->cfg.head_kind; k.B = B; k.S = S; k.Sp = round_up(S, 64); k.C = C;
     k.gs_mode = e->gs_mode; k.mx = e->mx && e->mx_built ? 1 : 0; k.mx_attn = e->mx_attn ? 1 : 0; k.ln_fused = e->ln_fused ? 1 : 0;
     k.prune = e->prune_last ? 1 : 0; k.attn_impl = e->attn_impl; k.prec_mask = e->prec_mask; k.act_sc = e->act_sc; k.sticky = e->fp8_sticky_off ? 1 : 0;
     k.full_lines = glc_gemm_full_lines(); k.mx_small = e->mx_small;
@@ -1330,6 +1357,20 @@ bool upload_head(glc_engine* e, const float* const* ht) {
         if (i % 2 == 0 && e->w_presplit) KCHK(glc_launch_presplit(e->stream, e->headw[i], H * H), false);
     }
     if (!upload_scorer(e, ht + GLC_TENSORS_HEAD)) return false;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); return false; }
+    return true;
+}
+
+// The sequence-classification head's six slots (include/gliclass_hip.h; create has checked which may be null), then the load's final sync
+bool upload_cls_head(glc_engine* e, const float* const* ht) {
+    const size_t H = e->cfg.hidden, K = e->cfg.cls_labels;
+    const size_t n[GLC_TENSORS_CLS_HEAD] = {H * H, H, H, H, K * H, K};
+    for (int i = 0; i < GLC_TENSORS_CLS_HEAD; ++i) {
+        if (!ht[i]) continue;
+        e->clsw[i] = upload_f32(e, ht[i], n[i]);
+        if (!e->clsw[i]) return false;
+        if (i == 0 && e->w_presplit) KCHK(glc_launch_presplit(e->stream, e->clsw[0], H * H), false);
+    }
     if (hipStreamSynchronize(e->stream) != hipSuccess) { glc_set_err(std::string("engine_create: ") + hipGetErrorString(hipGetLastError())); return false; }
     return true;
 }
@@ -1674,8 +1715,33 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (dtype != GLC_F32 && dtype != GLC_BF16 && dtype != GLC_F16) { glc_set_err("engine_create: bad dtype"); return nullptr; }
     if ((cfg->qk_norm & ~1) || (cfg->attn_bias & ~1)) { glc_set_err("engine_create: qk_norm and attn_bias must be 0 or 1"); return nullptr; }
     if (cfg->qk_norm && cfg->backbone != GLC_BACKBONE_DECODER) { glc_set_err("engine_create: qk_norm = 1 (per-head RMSNorm on Q and K) exists on the decoder backbone only"); return nullptr; }
+    const bool seqcls = cfg->head_kind == GLC_HEAD_SEQCLS;
+    if (cfg->head_kind != GLC_HEAD_GLICLASS && !seqcls) { glc_set_err("engine_create: head_kind must be 0 (GLiClass head) or 1 (sequence classification)"); return nullptr; }
+    if (!seqcls && (cfg->cls_labels || cfg->cls_act || cfg->cls_norm || cfg->cls_dense)) {
+        glc_set_err("engine_create: cls_labels, cls_act, cls_norm and cls_dense belong to head_kind = 1 (sequence classification); head_kind = 0 needs them 0"); return nullptr;
+    }
+    if (seqcls) {
+        // (before anything touches a device: a refusal of the configuration alone)
+        if (cfg->backbone == GLC_BACKBONE_DECODER) { glc_set_err("engine_create: head_kind = 1 (sequence classification) is not available on the decoder backbone (decoder ...ForSequenceClassification heads are out of scope)"); return nullptr; }
+        if (cfg->backbone == GLC_BACKBONE_T5) { glc_set_err("engine_create: head_kind = 1 (sequence classification) is not available on the T5 backbone (T5ForSequenceClassification needs the decoder stack)"); return nullptr; }
+        if (cfg->cls_labels < 1 || cfg->cls_labels > GLC_CLS_MAX_LABELS) { glc_set_err("engine_create: cls_labels must be 1 .. 1024"); return nullptr; }
+        if (cfg->cls_act < GLC_CLS_ACT_NONE || cfg->cls_act > GLC_CLS_ACT_GELU) { glc_set_err("engine_create: cls_act must be 0 (none), 1 (tanh) or 2 (gelu)"); return nullptr; }
+        if ((cfg->cls_norm & ~1) || (cfg->cls_dense & ~1)) { glc_set_err("engine_create: cls_norm and cls_dense must be 0 or 1"); return nullptr; }
+        if (cfg->pooling != GLC_POOL_FIRST && cfg->pooling != GLC_POOL_AVG) { glc_set_err("engine_create: head_kind = 1 pools 'first' or 'avg' (pooling)"); return nullptr; }
+        if (cfg->hidden > 2048) { glc_set_err("engine_create: head_kind = 1 needs hidden <= 2048"); return nullptr; }
+    }
     if (n_tensors != glc_num_tensors_cfg(cfg)) { glc_set_err("engine_create: wrong tensor count"); return nullptr; }
-    for (int i = 0; i < n_tensors; ++i) if (!tensors[i]) { glc_set_err("engine_create: null tensor"); return nullptr; }
+    {
+        // the optional slots of the sequence-classification head may be null (include/gliclass_hip.h); nothing else may
+        const int h0 = n_tensors - GLC_TENSORS_CLS_HEAD;
+        for (int i = 0; i < n_tensors; ++i) {
+            const int k = seqcls ? i - h0 : -1;
+            const bool must_null = (k == 0 || k == 1) ? !cfg->cls_dense : (k == 2 || k == 3) ? !cfg->cls_norm : false;
+            const bool may_null = must_null || k == 1 || k == 3 || k == 5;
+            if (must_null && tensors[i]) { glc_set_err("engine_create: a dense / norm tensor of the sequence-classification head is given although cls_dense / cls_norm = 0"); return nullptr; }
+            if (!tensors[i] && !may_null) { glc_set_err("engine_create: null tensor"); return nullptr; }
+        }
+    }
     const bool dec = cfg->backbone == GLC_BACKBONE_DECODER, mb = cfg->backbone == GLC_BACKBONE_MODERNBERT, bert = cfg->backbone == GLC_BACKBONE_BERT;
     const bool t5 = cfg->backbone == GLC_BACKBONE_T5;
     if (cfg->backbone != GLC_BACKBONE_DEBERTA && !dec && !mb && !bert && !t5) { glc_set_err("engine_create: unknown backbone"); return nullptr; }
@@ -1752,7 +1818,8 @@ glc_engine* glc_engine_create(const glc_model_config* cfg, const float* const* t
     if (!e->emb || !upload_as(e, tensors[0], nemb, e->emb, staging)) return fail();
     const bool loaded = dec ? create_decoder(e, tensors, staging) : mb ? create_modernbert(e, tensors, staging) : bert ? create_bert(e, tensors, staging)
                             : t5 ? create_t5(e, tensors, staging) : create_deberta(e, tensors, staging);
-    if (!loaded || !upload_head(e, tensors + n_tensors - GLC_TENSORS_HEAD - glc_num_scorer_tensors(cfg->scorer))) return fail();
+    if (!loaded || !(seqcls ? upload_cls_head(e, tensors + n_tensors - GLC_TENSORS_CLS_HEAD)
+                            : upload_head(e, tensors + n_tensors - GLC_TENSORS_HEAD - glc_num_scorer_tensors(cfg->scorer)))) return fail();
     // ModernBERT: the MX pipeline is opt-in; the environment makes the call glc_engine_enable_mx documents (read once, here).  An engine it does
     // not fit stays as it is: not an error.
     if (mb) {
@@ -1977,10 +2044,24 @@ static void plan_buckets(const std::vector<int>& len, int max_groups, const Buck
 int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S, float* logits, int c_alloc, int* c_out) {
     if (!e || !ids || !mask || (!logits && c_alloc > 0)) { glc_set_err("forward: null argument"); return -1; }
     if (!check_shape(e, B, S, c_alloc)) return -1;
+    const bool seqcls = e->cfg.head_kind == GLC_HEAD_SEQCLS;
+    const int K = e->cfg.cls_labels;
+    if (seqcls && c_alloc < K) {
+        glc_set_err("forward: this engine has a sequence-classification head with " + std::to_string(K) + " labels: c_alloc = " + std::to_string(c_alloc) + " is too small (c_alloc >= cls_labels)");
+        return -1;
+    }
+    // the head writes rows of K logits: the forward runs on the caller's buffer as [B, K], and a wider stride is made at the end, in place
+    // and from the last row down (columns k >= K of a row are then unspecified)
+    const int c_caller = c_alloc;
+    if (seqcls) c_alloc = K;
+    auto finish = [&]() {
+        if (c_out) *c_out = K;
+        for (int b = B - 1; b >= 1 && c_caller > K; --b) memmove(logits + (size_t)b * c_caller, logits + (size_t)b * K, (size_t)K * sizeof(float));
+    };
     // A class token under attention_mask 0 is outside the contract: its hidden state would be a padding-QUERY row (HF: uniform
     // attention over every position), which this engine does not compute — refuse instead of returning a different number.  The
     // reference's tokenizer never produces it (mask 1 on every real token, /root/reference/src/tokenizer.c:77-79).
-    for (size_t i = 0, n = (size_t)B * S; i < n; ++i)
+    for (size_t i = 0, n = seqcls ? 0 : (size_t)B * S; i < n; ++i)      // (the sequence-classification head reads no class token)
         if (mask[i] == 0 && ids[i] == e->cfg.class_token_index) {
             glc_set_err("forward: a class token (<<LABEL>>) lies under attention_mask 0 (row " + std::to_string(i / S) + ", position " + std::to_string(i % S) + "): not supported");
             return -1;
@@ -2029,6 +2110,7 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
             int cmax = 0;
             for (int b = 0; b < B; ++b) cmax = cnt[b] > cmax ? cnt[b] : cmax;
             if (c_out) *c_out = cmax;
+            if (seqcls) finish();
             e->last_groups = (int)cuts.size() - 1;
             e->last_graph = lg;
             return 0;
@@ -2039,6 +2121,7 @@ int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, i
     int cmax = 0;
     for (int b = 0; b < B; ++b) cmax = cnt[b] > cmax ? cnt[b] : cmax;
     if (c_out) *c_out = cmax;
+    if (seqcls) finish();
     return 0;
 }
 
@@ -2070,6 +2153,10 @@ int glc_engine_set_length_buckets(glc_engine* e, int max_groups) {
 int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_mask, int B, int S, int C, void* d_logits) {
     if (!e || !d_ids || !d_mask || (!d_logits && C > 0)) { glc_set_err("forward_device: null argument"); return -1; }
     if (!check_shape(e, B, S, C)) return -1;
+    if (e->cfg.head_kind == GLC_HEAD_SEQCLS && C != e->cfg.cls_labels) {
+        glc_set_err("forward_device: this engine has a sequence-classification head with " + std::to_string(e->cfg.cls_labels) + " labels: C = " + std::to_string(C) + " must equal cls_labels");
+        return -1;
+    }
     std::lock_guard<std::mutex> lk(e->mu);
     HIPCHK(hipSetDevice(e->device), -1);
     if (!ensure_capacity(e, B, S, C)) return -1;
@@ -2081,6 +2168,19 @@ int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_ma
     // fp8 range guard (forward_one): a device-resident forward cannot be repeated behind the caller's back — the counter travels to a pinned
     // slot behind it, and glc_engine_sync reports a forward that left the range (and moves the engine to the split arithmetic)
     if (e->last_mx) { HIPCHK(hipMemcpyAsync(e->h_gxsat, e->d_gxsat, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, e->stream), -1); e->fp8_device_pending = true; }
+    return 0;
+}
+
+/* Zero-shot NLI reduction over pair logits (include/gliclass_hip.h) */
+int glc_engine_nli_scores(glc_engine* e, const float* d_logits, int T, int Lb, int entail_id, int contra_id, int multi_label, float* d_probs) {
+    if (!e) { glc_set_err("nli_scores: null engine"); return -1; }
+    if (!d_logits || !d_probs) { glc_set_err("nli_scores: null argument"); return -1; }
+    if (e->cfg.head_kind != GLC_HEAD_SEQCLS) { glc_set_err("nli_scores: this engine has the GLiClass head; NLI scores need a sequence-classification head (head_kind = 1)"); return -1; }
+    if (e->cfg.cls_labels < 2) { glc_set_err("nli_scores: the head has " + std::to_string(e->cfg.cls_labels) + " label; entailment and contradiction need cls_labels >= 2"); return -1; }
+    std::lock_guard<std::mutex> lk(e->mu);
+    HIPCHK(hipSetDevice(e->device), -1);
+    KCHK(glc_launch_nli_scores(e->stream, d_logits, T, Lb, e->cfg.cls_labels, entail_id, contra_id, multi_label, d_probs), -1);
+    HIPCHK(hipGetLastError(), -1);
     return 0;
 }
 

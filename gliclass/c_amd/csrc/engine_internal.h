@@ -67,12 +67,12 @@ struct LayerW {
 // Captured-graph replay (glc_engine_set_graph_replay): what a cached forward is filed under — everything that decides which kernels a forward
 // launches or what arguments they get — and what it leaves behind for the glc_debug_last_forward_* queries
 struct GraphKey {
-    int backbone, B, S, Sp, C;
+    int backbone, head, B, S, Sp, C;      // head: the head kind (constant per engine; kept in the key so that the key alone names the captured launch sequence)
     int gs_mode, mx, mx_attn, ln_fused, prune, attn_impl, prec_mask, act_sc, sticky, full_lines, mx_small;
     unsigned long long ws_gen;
     const void *ids, *mask, *logits;
     bool operator==(const GraphKey& o) const {
-        return backbone == o.backbone && B == o.B && S == o.S && Sp == o.Sp && C == o.C && gs_mode == o.gs_mode && mx == o.mx && mx_attn == o.mx_attn &&
+        return backbone == o.backbone && head == o.head && B == o.B && S == o.S && Sp == o.Sp && C == o.C && gs_mode == o.gs_mode && mx == o.mx && mx_attn == o.mx_attn &&
                ln_fused == o.ln_fused && prune == o.prune && attn_impl == o.attn_impl && prec_mask == o.prec_mask && act_sc == o.act_sc &&
                sticky == o.sticky && full_lines == o.full_lines && mx_small == o.mx_small && ws_gen == o.ws_gen && ids == o.ids && mask == o.mask && logits == o.logits;
     }
@@ -153,6 +153,7 @@ struct glc_engine {
     float* headw[8] = {nullptr};
     float* scw[8] = {nullptr};           // the scorer's own tensors (weighted-dot: 8, mlp: 6, simple: none), fp32
     float* scorer_ws = nullptr;          // its row buffers
+    float* clsw[GLC_TENSORS_CLS_HEAD] = {nullptr};      // sequence-classification head (head_kind 1): dense.w (pre-split) / .b, norm.w / .b, classifier.w / .b; null = absent
     int P = 0;
     // workspace
     int capM = 0, capB = 0, capIds = 0, capC = 0, capHeadRows = 0, capSel = 0, capGU = 0;

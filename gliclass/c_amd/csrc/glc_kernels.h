@@ -276,6 +276,16 @@ const char* glc_launch_relu_dot(hipStream_t st, const float* X, const float* w, 
 // normalize_features ahead of those scorers: X[r][:] /= (|X[r]| + 1e-8), rows x H fp32 in place
 const char* glc_launch_l2norm_rows(hipStream_t st, float* X, int rows, int H);
 
+// ---- sequence-classification head (cls_head.hip; head_kind = GLC_HEAD_SEQCLS) ----
+// logits[b, k] = <n(act(X[b, :])), cls_w[k, :]> + cls_b[k] for b < B, k < K: X fp32 [B, H] (the dense stage's output, or the pooled rows when the
+// head has no dense stage); act 0 none / 1 tanh / 2 erf-GELU; n = LayerNorm (gain norm_w, bias norm_b or none, epsilon eps; fp32 statistics)
+// when norm_w is given, else the identity; cls_b null = no bias.  One launch, one wave per row; H % 4 == 0, H <= 2048, 1 <= K <= 1024.
+const char* glc_launch_cls_head(hipStream_t st, const float* X, const float* norm_w, const float* norm_b, const float* cls_w, const float* cls_b,
+                                float* logits, int B, int H, int K, int act, float eps);
+// zero-shot NLI reduction (transformers pipelines/zero_shot_classification.py postprocess): pair logits [T * Lb, K] -> probs [T, Lb];
+// multi_label: softmax over (contra_id, entail_id) per pair, the entailment share; else softmax of the entail_id logits over a text's Lb labels
+const char* glc_launch_nli_scores(hipStream_t st, const float* logits, int T, int Lb, int K, int entail_id, int contra_id, int multi_label, float* probs);
+
 // Pruned last layer: compact the rows the head reads. Row r < B: [CLS] of sequence r; row B + b*C + j: class
 // token j of sequence b (sequence start if absent). Writes Xs[r,:] = X[row,:] and the (sequence, position) lists.
 // klen given ('last' pooling): row r < B is the last attended token of sequence r (klen[r] - 1; 0 for an empty row), as glc_launch_head_gather.

@@ -1,12 +1,13 @@
 """Thin Python handle over the HIP engine C-ABI (tests, bench.py, smoke).  All compute happens in
 libgliclass_hip.so; this module only marshals numpy buffers."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
 from . import _lib
-from .config import GLiClassConfig
-from .weights import tensor_specs
+from .config import GLiClassConfig, HEAD_SEQCLS
+from .weights import tensor_specs, CLS_HEAD_NAMES, CLS_OPTIONAL_BIASES
 
 DTYPES = {"f32": 0, "bf16": 1, "f16": 2}
 DTYPE_NAMES = {v: k for k, v in DTYPES.items()}
@@ -18,7 +19,7 @@ def to_c_config(cfg: GLiClassConfig) -> _lib.ModelConfig:
                             cfg.pooling, cfg.scorer, cfg.embed_class_token, cfg.normalize_features, cfg.backbone, cfg.kv_heads,
                             cfg.causal, cfg.ln_eps, cfg.logit_scale, cfg.rope_theta, cfg.local_window, cfg.global_every,
                             cfg.rope_theta_local, cfg.qk_norm, cfg.attn_bias, cfg.max_positions, cfg.type_vocab, cfg.pos_offset,
-                            cfg.rel_buckets, cfg.rel_max_distance)
+                            cfg.rel_buckets, cfg.rel_max_distance, cfg.head_kind, cfg.cls_labels, cfg.cls_act, cfg.cls_norm, cfg.cls_dense)
 
 
 def delta_table(S, bucket_size=256, max_position=512):
@@ -39,9 +40,15 @@ class Engine:
         self.L = _lib.hip()
         self.cfg = cfg
         self.dtype = dtype
-        names = [s[0] for s in tensor_specs(cfg)]
-        arrs = [np.ascontiguousarray(tensors[n], np.float32) for n in names]
-        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        if cfg.head_kind == HEAD_SEQCLS:
+            # the six head slots of the C-ABI; a tensor the checkpoint does not have (no dense stage, no norm, a bias switched off) is a null pointer
+            names = [s[0] for s in tensor_specs(dataclasses.replace(cfg, cls_dense=1, cls_norm=1))]
+            have = {s[0] for s in tensor_specs(cfg)}
+            absent = {n for n in CLS_HEAD_NAMES if n not in have or (n in CLS_OPTIONAL_BIASES and tensors.get(n) is None)}
+        else:
+            names, absent = [s[0] for s in tensor_specs(cfg)], set()
+        arrs = [None if n in absent else np.ascontiguousarray(tensors[n], np.float32) for n in names]
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
         cc = to_c_config(cfg)
         self.h = self.L.glc_engine_create(C.byref(cc), ptrs, len(arrs), device, DTYPES[dtype])
         if not self.h:
@@ -83,13 +90,37 @@ class Engine:
         mask = np.ascontiguousarray(mask, np.int64)
         B, S = ids.shape
         if c_alloc is None:
-            c_alloc = int((ids == self.cfg.class_token_index).sum(1).max())
+            c_alloc = self.cfg.cls_labels if self.cfg.head_kind == HEAD_SEQCLS else int((ids == self.cfg.class_token_index).sum(1).max())
         logits = np.zeros((B, max(c_alloc, 1)), np.float32)
         c_out = C.c_int(0)
         if self.L.glc_engine_forward(self.h, ids.ctypes.data, mask.ctypes.data, B, S, logits.ctypes.data, c_alloc, C.byref(c_out)) != 0:
             raise self._err("glc_engine_forward")
         self.last_c = c_out.value
         return logits[:, :c_alloc]
+
+    def num_labels(self):
+        """width of the classifier output of a sequence-classification engine (head_kind 1); 0 with the GLiClass head"""
+        return int(self.L.glc_engine_config(self.h).contents.cls_labels)
+
+    def nli_scores(self, logits, T, Lb, entail_id, contra_id, multi_label=False):
+        """zero-shot NLI: pair logits [T * Lb, K] (pair (t, l) in row t * Lb + l, as a forward of the pair batch returns them) -> probabilities
+        [T, Lb] on the device, with the semantics of transformers' zero-shot pipeline: multi_label = the entailment share of softmax over
+        (contradiction, entailment) per pair; else softmax of the entailment logits over a text's labels"""
+        logits = np.ascontiguousarray(logits, np.float32)
+        if logits.shape != (T * Lb, self.cfg.cls_labels):
+            raise ValueError(f"nli_scores: logits {logits.shape}, expected {(T * Lb, self.cfg.cls_labels)}")
+        out = np.zeros((T, Lb), np.float32)
+        d_in, d_out = self.dev_alloc(max(logits.nbytes, 4)), self.dev_alloc(max(out.nbytes, 4))
+        try:
+            self.h2d(d_in, logits)
+            if self.L.glc_engine_nli_scores(self.h, d_in, T, Lb, int(entail_id), int(contra_id), int(bool(multi_label)), d_out) != 0:
+                raise self._err("glc_engine_nli_scores")
+            self.sync()
+            self.d2h(out, d_out)
+        finally:
+            self.dev_free(d_in)
+            self.dev_free(d_out)
+        return out
 
     def hidden(self, which, B, S):
         out = np.zeros((B, S, self.cfg.hidden), np.float32)

@@ -76,6 +76,17 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
     if (!gj_is(enc, GJ_OBJ)) enc = root;                                  /* a bare backbone config */
     const char* mt = jtext(enc, "model_type");
     if (!mt) REJECT("no model_type");
+    /* (a *ForSequenceClassification checkpoint — the block at the end of this function — on a backbone that has no such head here) */
+    const gj_value* archs = gj_get(root, "architectures");
+    int seqcls = 0;
+    if (gj_is(archs, GJ_ARR))
+        for (size_t i = 0; i < archs->u.arr.n; ++i) {
+            const gj_value* a = archs->u.arr.items[i];
+            static const char sfx[] = "ForSequenceClassification";
+            if (gj_is(a, GJ_STR) && a->u.str.len >= sizeof sfx - 1 && !strcmp(a->u.str.s + a->u.str.len - (sizeof sfx - 1), sfx)) seqcls = 1;
+        }
+    if (seqcls && strcmp(mt, "deberta-v2") && strcmp(mt, "bert") && strcmp(mt, "roberta") && strcmp(mt, "xlm-roberta") && strcmp(mt, "modernbert"))
+        REJECT("model_type '%s' has no sequence-classification head in this engine (deberta-v2, bert, roberta, xlm-roberta, modernbert; decoder and T5 classes are out of scope)", mt);
     const char* arch = jtext(root, "architecture_type");
     if (arch && strcmp(arch, "uni-encoder")) REJECT("architecture_type '%s' is not implemented (only uni-encoder)", arch);
     if (jflag(root, "use_lstm", 0)) REJECT("use_lstm=true is not implemented");
@@ -262,7 +273,45 @@ static int parse_config(const gj_value* root, glc_model_config* c) {
                    c->rel_buckets, c->rel_max_distance);
         if (c->pad_id < 0) REJECT("pad_token_id %d is negative", c->pad_id);
     } else REJECT("backbone model_type '%s' is not implemented (deberta-v2, qwen2, qwen3, llama, modernbert, bert, roberta, xlm-roberta, t5, mt5)", mt);
+    /* A checkpoint saved by an HF *ForSequenceClassification class (`architectures` names it; a bare HF config, no GLiClass wrapper keys):
+     * the sequence-classification head (head_kind = GLC_HEAD_SEQCLS, include/gliclass_hip.h) behind the backbone parsed above.  Mirrors
+     * seqcls_config_from_hf of gliclass/c_amd/weights.py; the head arithmetic per class and its transformers sources: csrc/cls_head.hip. */
+    if (seqcls) {
+        const gj_value* i2l = gj_get(root, "id2label");
+        const int K = gj_is(i2l, GJ_OBJ) && i2l->u.obj.n > 0 ? (int)i2l->u.obj.n : (int)jnum(root, "num_labels", 2);
+        if (K < 1 || K > GLC_CLS_MAX_LABELS) REJECT("num_labels %d is not implemented (1 .. %d)", K, GLC_CLS_MAX_LABELS);
+        c->head_kind = GLC_HEAD_SEQCLS; c->cls_labels = K; c->cls_dense = 1; c->cls_norm = 0; c->pooling = GLC_POOL_FIRST;
+        c->scorer = GLC_SCORER_DOT;
+        if (c->backbone == GLC_BACKBONE_BERT) c->cls_act = GLC_CLS_ACT_TANH;                 /* BertPooler / RobertaClassificationHead */
+        else if (c->backbone == GLC_BACKBONE_MODERNBERT) {                                   /* ModernBertPredictionHead */
+            const char* act = jtext(root, "classifier_activation");
+            if (act && strcmp(act, "gelu")) REJECT("classifier_activation '%s' is not implemented (gelu)", act);
+            const char* cp = jtext(root, "classifier_pooling");
+            if (cp && strcmp(cp, "cls") && strcmp(cp, "mean")) REJECT("classifier_pooling '%s' is not implemented (cls, mean)", cp);
+            c->pooling = cp && !strcmp(cp, "mean") ? GLC_POOL_AVG : GLC_POOL_FIRST;
+            c->cls_act = GLC_CLS_ACT_GELU; c->cls_norm = 1;
+        } else {                                                                             /* DeBERTa ContextPooler */
+            const int phs = (int)jnum(root, "pooler_hidden_size", (double)c->hidden);
+            if (phs != c->hidden) REJECT("pooler_hidden_size %d != hidden_size %d is not implemented", phs, c->hidden);
+            const char* act = jtext(root, "pooler_hidden_act");
+            if (act && strcmp(act, "gelu")) REJECT("pooler_hidden_act '%s' is not implemented (gelu)", act);
+            c->cls_act = GLC_CLS_ACT_GELU;
+        }
+    }
     return 0;
+}
+
+/* checkpoint name of slot k of the sequence-classification head (include/gliclass_hip.h order) for the class the config names; NULL: the class
+ * has no such tensor.  Looked up under the importer's prefixes ("" and "bert." among them: DeBERTa's pooler sits at the top level, BERT's
+ * inside the backbone). */
+static const char* cls_head_key(const glc_model_config* c, int k) {
+    static const char* const pooler[6] = {"pooler.dense.weight", "pooler.dense.bias", NULL, NULL, "classifier.weight", "classifier.bias"};
+    static const char* const roberta[6] = {"classifier.dense.weight", "classifier.dense.bias", NULL, NULL, "classifier.out_proj.weight", "classifier.out_proj.bias"};
+    static const char* const mbert[6] = {"head.dense.weight", "head.dense.bias", "head.norm.weight", "head.norm.bias", "classifier.weight", "classifier.bias"};
+    if (k < 0 || k >= GLC_TENSORS_CLS_HEAD) return NULL;
+    if (c->backbone == GLC_BACKBONE_MODERNBERT) return mbert[k];
+    if (c->backbone == GLC_BACKBONE_BERT && c->pos_offset != 0) return roberta[k];           /* RoBERTa / XLM-R (BERT numbers positions from 0) */
+    return pooler[k];
 }
 
 typedef struct { const gj_value* hdr; const unsigned char* data; size_t data_len; } st_file;
@@ -397,6 +446,18 @@ int glc_load_hf_checkpoint(const char* path, glc_weights* w) {
     for (int i = 0; i < w->n_tensors; ++i) {
         int nd = glc_tensor_spec(c, i, tn, shp, &amp, &mean);
         size_t n = (size_t)shp[0] * (nd > 1 ? (size_t)shp[1] : 1);
+        /* sequence-classification head: the class's own names; a bias the checkpoint has switched off (ModernBERT classifier_bias /
+         * norm_bias = false) and a stage the class does not have stay NULL (glc_engine_create decides which slots may be empty) */
+        if (c->head_kind == GLC_HEAD_SEQCLS && i >= w->n_tensors - GLC_TENSORS_CLS_HEAD) {
+            const int k = i - (w->n_tensors - GLC_TENSORS_CLS_HEAD);
+            const char* key = cls_head_key(c, k);
+            const int optional = k == 1 || k == 3 || k == 5;
+            if (!key || (optional && !st_find(&st, key, found, sizeof found))) continue;
+            if (st_read_f32(&st, stp, key, nd, shp, w->_owned + off)) goto done;
+            w->tensors[i] = w->_owned + off;
+            off += (n + 15) / 16 * 16;
+            continue;
+        }
         /* BERT family: the fused Wqkv rows (and bias) are the checkpoint's query | key | value tensors, one after the other */
         const char* fq = c->backbone == GLC_BACKBONE_BERT ? strstr(tn, ".attention.self.Wqkv.") : NULL;
         if (fq) {

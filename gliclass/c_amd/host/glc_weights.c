@@ -144,6 +144,18 @@ static int head_spec(const glc_model_config* c, int k, char* name, uint64_t shap
     char buf[96];
 #define SPEC1(nm, n0, a, m) do { snprintf(name, 96, "%s", nm); shape[0] = (n0); *amp = (a); *mean = (m); return 1; } while (0)
 #define SPEC2(nm, n0, n1, a) do { snprintf(name, 96, "%s", nm); shape[0] = (n0); shape[1] = (n1); *amp = (a); return 2; } while (0)
+    if (c->head_kind == GLC_HEAD_SEQCLS) {      /* the six slots of include/gliclass_hip.h (mirrors head_specs of weights.py); a blob may leave slots out (load_blob) */
+        const uint64_t K = (uint64_t)c->cls_labels;
+        switch (k) {
+            case 0: SPEC2("cls.dense.weight", H, H, lin_amp(1.0, (double)H));
+            case 1: SPEC1("cls.dense.bias", H, 0.5, 0.0);
+            case 2: SPEC1("cls.norm.weight", H, 0.5, 1.5);
+            case 3: SPEC1("cls.norm.bias", H, 0.3, 0.1);
+            case 4: SPEC2("cls.classifier.weight", K, H, lin_amp(2.0, (double)H));
+            case 5: SPEC1("cls.classifier.bias", K, 0.5, 0.0);
+            default: return -1;
+        }
+    }
     if (k < 0 || k >= GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer)) return -1;
     if (k < GLC_TENSORS_HEAD) {
         const double t2 = sqrt(1.5 / sqrt((double)H)) / 0.7;
@@ -409,7 +421,8 @@ static int load_blob(const char* path, glc_weights* w) {
     c->qk_norm = 0; c->attn_bias = 1;         /* what every blob older than version 4 means */
     c->max_positions = 0; c->type_vocab = 0; c->pos_offset = 0;      /* ... and every blob older than version 5 */
     c->rel_buckets = 0; c->rel_max_distance = 0;                     /* ... and every blob older than version 6 */
-    if (ver >= 3 && ver <= 6) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
+    c->head_kind = 0; c->cls_labels = 0; c->cls_act = 0; c->cls_norm = 0; c->cls_dense = 0;      /* ... and older than version 7 */
+    if (ver >= 3 && ver <= 7) {          /* 3: written for the ModernBERT backbone only: + local_window, global_every, rope_theta_local */
         int32_t i3[2];
         float f3;
         memcpy(i3, b + 16 + sizeof ints + sizeof fl, sizeof i3);
@@ -423,36 +436,54 @@ static int load_blob(const char* path, glc_weights* w) {
                 int32_t i5[3];
                 memcpy(i5, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3 + sizeof i4, sizeof i5);
                 c->max_positions = i5[0]; c->type_vocab = i5[1]; c->pos_offset = i5[2];
-                if (ver == 6) {  /* written for the T5 backbone only: + rel_buckets, rel_max_distance */
+                if (ver >= 6) {  /* written for the T5 backbone only: + rel_buckets, rel_max_distance */
                     int32_t i6[2];
                     memcpy(i6, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3 + sizeof i4 + sizeof i5, sizeof i6);
                     c->rel_buckets = i6[0]; c->rel_max_distance = i6[1];
+                    if (ver == 7) {  /* written for the sequence-classification head only (any backbone that has it): + head_kind .. cls_dense */
+                        int32_t i7[5];
+                        memcpy(i7, b + 16 + sizeof ints + sizeof fl + sizeof i3 + sizeof f3 + sizeof i4 + sizeof i5 + sizeof i6, sizeof i7);
+                        c->head_kind = i7[0]; c->cls_labels = i7[1]; c->cls_act = i7[2]; c->cls_norm = i7[3]; c->cls_dense = i7[4];
+                    }
                 }
             }
         }
     }
-    const int bert_bad = (c->backbone == GLC_BACKBONE_BERT) != (ver == 5) ||
-                         (ver == 5 && (c->max_positions < 1 || c->max_positions > (1 << 24) || c->type_vocab < 1 || c->type_vocab > (1 << 16) ||
+    const int v7 = ver == 7;      /* carries every older slot: the backbone's own version is the one its fields would have been written as */
+    const int cls_bad = v7 != (c->head_kind == GLC_HEAD_SEQCLS) ||
+                        (v7 && (c->cls_labels < 1 || c->cls_labels > GLC_CLS_MAX_LABELS || c->cls_act < 0 || c->cls_act > 2 || (c->cls_norm & ~1) || (c->cls_dense & ~1) ||
+                                c->backbone == GLC_BACKBONE_DECODER || c->backbone == GLC_BACKBONE_T5));
+    const int bert_bad = (c->backbone == GLC_BACKBONE_BERT) != (ver == 5 || (v7 && c->max_positions > 0)) ||
+                         (c->backbone == GLC_BACKBONE_BERT && (c->max_positions < 1 || c->max_positions > (1 << 24) || c->type_vocab < 1 || c->type_vocab > (1 << 16) ||
                                        c->pos_offset < 0 || c->max_positions - c->pos_offset < 1));
     const int t5_bad = (c->backbone == GLC_BACKBONE_T5) != (ver == 6) ||
                        (ver == 6 && (c->rel_buckets < 4 || c->rel_buckets % 4 || c->rel_buckets > (1 << 16) || c->rel_max_distance <= c->rel_buckets / 4 ||
                                      c->heads < 1 || c->heads > (1 << 12)));
-    if (ver < 2 || ver > 6 || bert_bad || t5_bad || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 || (int)nt != glc_num_tensors_cfg(c)) {
+    /* (a version-7 blob records only the head tensors that exist: nt may fall short of the slot count by the absent ones) */
+    const int nslots = glc_num_tensors_cfg(c);
+    if (ver < 2 || ver > 7 || cls_bad || bert_bad || t5_bad || (c->qk_norm & ~1) || (c->attn_bias & ~1) || c->layers <= 0 || c->layers > 4096 ||
+        (v7 ? ((int)nt > nslots || (int)nt < nslots - GLC_TENSORS_CLS_HEAD + 1) : (int)nt != nslots)) {
         fprintf(stderr, "Error: '%s': unsupported GLCW header (version %u, %u tensors)\n", path, ver, nt);
         return -1;
     }
-    w->n_tensors = (int)nt;
-    w->tensors = (const float**)calloc(nt, sizeof(float*));
+    w->n_tensors = nslots;
+    w->tensors = (const float**)calloc((size_t)nslots, sizeof(float*));
     if (!w->tensors) return -1;
     char want[96];
     uint64_t shp[4];
     double amp, mean;
-    for (uint32_t i = 0; i < nt; ++i) {
-        const unsigned char* r = b + GLCW_HEADER_BYTES + (size_t)i * GLCW_REC_BYTES;
+    const int head0 = nslots - GLC_TENSORS_CLS_HEAD;
+    uint32_t slot = 0;
+    for (uint32_t rec = 0; rec < nt; ++rec, ++slot) {
+        const unsigned char* r = b + GLCW_HEADER_BYTES + (size_t)rec * GLCW_REC_BYTES;
         if ((size_t)(r - b) + GLCW_REC_BYTES > w->_map_len) { fprintf(stderr, "Error: '%s' truncated\n", path); return -1; }
         uint32_t dt, nd;
         uint64_t shape[4], off, nb;
         memcpy(&dt, r + 96, 4); memcpy(&nd, r + 100, 4); memcpy(shape, r + 104, 32); memcpy(&off, r + 136, 8); memcpy(&nb, r + 144, 8);
+        /* version 7: a head slot whose name this record does not carry is a tensor the checkpoint does not have (its pointer stays NULL;
+         * glc_engine_create decides whether that slot may be empty) */
+        while (v7 && (int)slot >= head0 && (int)slot < nslots - 1 && glc_tensor_spec(c, (int)slot, want, shp, &amp, &mean) > 0 && strncmp((const char*)r, want, 96) != 0) ++slot;
+        const uint32_t i = slot;
         int wnd = glc_tensor_spec(c, (int)i, want, shp, &amp, &mean);
         if (wnd < 0 || strncmp((const char*)r, want, 96) != 0 || dt != 0 || (int)nd != wnd || shape[0] != shp[0] ||
             (wnd > 1 && shape[1] != shp[1]) || off % 4 || off + nb > w->_map_len || nb != 4 * shp[0] * (wnd > 1 ? shp[1] : 1)) {

@@ -247,6 +247,7 @@ static OrtValue* run_on_engine(OrtSession* s, glc_engine* e, OrtValue* ids_t, Or
         for (int t = 0; t < S; ++t) c += ids[(size_t)b * S + t] == s->cfg.class_token_index;
         if (c > C) C = c;
     }
+    if (s->cfg.head_kind == GLC_HEAD_SEQCLS) C = s->cfg.cls_labels;      /* sequence-classification head: [B, K] whatever the ids hold */
     float* logits = (float*)calloc((size_t)B * (C ? C : 1), sizeof(float));
     if (!logits) { fprintf(stderr, "Error during inference: out of memory\n"); return NULL; }
     int qi = 0;

@@ -16,7 +16,8 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from .config import GLiClassConfig, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, BACKBONE_T5, SCORER_WEIGHTED_DOT, SCORER_MLP, SCORER_MLP_HIDDEN
+from .config import (GLiClassConfig, BACKBONE_DEBERTA, BACKBONE_DECODER, BACKBONE_MODERNBERT, BACKBONE_BERT, BACKBONE_T5, SCORER_WEIGHTED_DOT, SCORER_MLP,
+                     SCORER_MLP_HIDDEN, HEAD_SEQCLS, CLS_ACT_TANH, CLS_ACT_GELU, CLS_MAX_LABELS, POOL_FIRST, POOL_AVG)
 from . import prng
 
 MAGIC = b"GLCW\x00\x01\x00\x00"
@@ -36,6 +37,13 @@ _V4_INT_FIELDS = ["qk_norm", "attn_bias"]
 _V5_INT_FIELDS = ["max_positions", "type_vocab", "pos_offset"]
 # version 6 (T5 backbone only): + rel_buckets, rel_max_distance (int32) after the v5 slots
 _V6_INT_FIELDS = ["rel_buckets", "rel_max_distance"]
+# version 7 (head_kind = 1, the sequence-classification head, only): + head_kind, cls_labels, cls_act, cls_norm, cls_dense (int32) after the v6 slots;
+# v7 carries every older slot whatever the backbone
+_V7_INT_FIELDS = ["head_kind", "cls_labels", "cls_act", "cls_norm", "cls_dense"]
+# the sequence-classification head's tensors in the order of include/gliclass_hip.h (blob names: "cls." + the name there); the biases that a
+# checkpoint may switch off (ModernBERT classifier_bias = false: dense.bias; norm_bias = false: norm.bias) are simply absent from the tensor dict and the blob
+CLS_HEAD_NAMES = ("cls.dense.weight", "cls.dense.bias", "cls.norm.weight", "cls.norm.bias", "cls.classifier.weight", "cls.classifier.bias")
+CLS_OPTIONAL_BIASES = ("cls.dense.bias", "cls.norm.bias", "cls.classifier.bias")
 
 
 def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float, float]]:
@@ -52,6 +60,16 @@ def tensor_specs(cfg: GLiClassConfig) -> List[Tuple[str, Tuple[int, ...], float,
         return s3 * t / math.sqrt(fan_in)
 
     def head_specs():
+        if cfg.head_kind == HEAD_SEQCLS:
+            # drawn with a visible spread: a dropped bias, a skipped activation (the dense output has a spread of ~1: tanh and GELU bend it) or a
+            # skipped norm (gain around 1.5, bias off zero) moves the logits by tenths
+            K = cfg.cls_labels
+            out = []
+            if cfg.cls_dense:
+                out += [("cls.dense.weight", (H, H), lin(1.0, H), 0.0), ("cls.dense.bias", (H,), 0.5, 0.0)]
+            if cfg.cls_norm:
+                out += [("cls.norm.weight", (H,), 0.5, 1.5), ("cls.norm.bias", (H,), 0.3, 0.1)]
+            return out + [("cls.classifier.weight", (K, H), lin(2.0, H), 0.0), ("cls.classifier.bias", (K,), 0.5, 0.0)]
         t2 = math.sqrt(1.5 / math.sqrt(H)) / 0.7
         out = []
         for proj in ("text_projector", "classes_projector"):
@@ -210,11 +228,12 @@ def make_weights(cfg: GLiClassConfig, seed: int = 42) -> Dict[str, np.ndarray]:
 
 def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
     d = cfg.asdict()
-    v6 = cfg.backbone == BACKBONE_T5                  # v6 carries the v3, v4 and v5 slots too
+    v7 = cfg.head_kind == HEAD_SEQCLS                 # v7 carries every older slot
+    v6 = v7 or cfg.backbone == BACKBONE_T5            # v6 carries the v3, v4 and v5 slots too
     v5 = v6 or cfg.backbone == BACKBONE_BERT          # v5 carries the v3 and v4 slots too
     v4 = v5 or (cfg.qk_norm, cfg.attn_bias) != (0, 1)       # Llama / Qwen3 decoders; v4 carries the v3 slots too
     v3 = cfg.backbone == BACKBONE_MODERNBERT          # every other backbone keeps writing byte-identical v2 headers
-    b = MAGIC + struct.pack("<II", 6 if v6 else 5 if v5 else 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
+    b = MAGIC + struct.pack("<II", 7 if v7 else 6 if v6 else 5 if v5 else 4 if v4 else 3 if v3 else 2, n_tensors)     # version 2: + backbone, kv_heads, causal, rope_theta
     b += struct.pack("<%di" % len(_INT_FIELDS), *[int(d[k]) for k in _INT_FIELDS])
     b += struct.pack("<%df" % len(_F32_FIELDS), *[float(d[k]) for k in _F32_FIELDS])
     if v3 or v4:
@@ -226,12 +245,14 @@ def _pack_header(cfg: GLiClassConfig, n_tensors: int) -> bytes:
         b += struct.pack("<%di" % len(_V5_INT_FIELDS), *[int(d[k]) for k in _V5_INT_FIELDS])
     if v6:
         b += struct.pack("<%di" % len(_V6_INT_FIELDS), *[int(d[k]) for k in _V6_INT_FIELDS])
+    if v7:
+        b += struct.pack("<%di" % len(_V7_INT_FIELDS), *[int(d[k]) for k in _V7_INT_FIELDS])
     assert len(b) <= HEADER_BYTES
     return b + b"\x00" * (HEADER_BYTES - len(b))
 
 
 def write_blob(path: str, cfg: GLiClassConfig, tensors: Dict[str, np.ndarray]) -> None:
-    names = [s[0] for s in tensor_specs(cfg)]
+    names = [s[0] for s in tensor_specs(cfg) if not (s[0] in CLS_OPTIONAL_BIASES and tensors.get(s[0]) is None)]
     missing = [n for n in names if n not in tensors]
     if missing:
         raise KeyError(f"missing tensors: {missing[:4]}...")
@@ -263,7 +284,7 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if hdr[:8] != MAGIC:
         raise ValueError("not a GLCW blob")
     ver, n_t = struct.unpack_from("<II", hdr, 8)
-    if ver not in (2, 3, 4, 5, 6):
+    if ver not in (2, 3, 4, 5, 6, 7):
         raise ValueError(f"unsupported GLCW version {ver}")
     ints = struct.unpack_from("<%di" % len(_INT_FIELDS), hdr, 16)
     flts = struct.unpack_from("<%df" % len(_F32_FIELDS), hdr, 16 + 4 * len(_INT_FIELDS))
@@ -282,6 +303,9 @@ def read_blob(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
     if ver >= 6:
         o6 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS) + len(_V4_INT_FIELDS) + len(_V5_INT_FIELDS))
         kw.update(dict(zip(_V6_INT_FIELDS, struct.unpack_from("<%di" % len(_V6_INT_FIELDS), hdr, o6))))
+    if ver >= 7:
+        o7 = 16 + 4 * (len(_INT_FIELDS) + len(_F32_FIELDS) + len(_V3_INT_FIELDS) + len(_V3_F32_FIELDS) + len(_V4_INT_FIELDS) + len(_V5_INT_FIELDS) + len(_V6_INT_FIELDS))
+        kw.update(dict(zip(_V7_INT_FIELDS, struct.unpack_from("<%di" % len(_V7_INT_FIELDS), hdr, o7))))
     cfg = GLiClassConfig(name="blob", **kw)
     tensors = {}
     for i in range(n_t):
@@ -449,3 +473,182 @@ def load_t5_checkpoint(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]
     cfg = t5_config_from_hf(root, vocab=emb[0].shape[0])
     del cfg0
     return cfg, from_state_dict(sd, cfg)
+
+
+# ---- *ForSequenceClassification checkpoints (head_kind = HEAD_SEQCLS; the arithmetic and its transformers sources: csrc/cls_head.hip) ----
+SEQCLS_MODEL_TYPES = ("deberta-v2", "bert", "roberta", "xlm-roberta", "modernbert")
+# checkpoint names of the six head slots (CLS_HEAD_NAMES order) per model_type; None = the class has no such tensor
+_SEQCLS_HEAD_KEYS = {
+    "deberta-v2": ("pooler.dense.weight", "pooler.dense.bias", None, None, "classifier.weight", "classifier.bias"),
+    "bert": ("bert.pooler.dense.weight", "bert.pooler.dense.bias", None, None, "classifier.weight", "classifier.bias"),
+    "roberta": ("classifier.dense.weight", "classifier.dense.bias", None, None, "classifier.out_proj.weight", "classifier.out_proj.bias"),
+    "modernbert": ("head.dense.weight", "head.dense.bias", "head.norm.weight", "head.norm.bias", "classifier.weight", "classifier.bias"),
+}
+_SEQCLS_HEAD_KEYS["xlm-roberta"] = _SEQCLS_HEAD_KEYS["roberta"]
+
+
+def _num_labels(root: dict) -> int:
+    if isinstance(root.get("id2label"), dict) and root["id2label"]:
+        return len(root["id2label"])
+    return int(root.get("num_labels", 2))
+
+
+def seqcls_config_from_hf(root: dict, vocab: int = None) -> GLiClassConfig:
+    """GLiClassConfig of a *ForSequenceClassification checkpoint's config.json (a bare HF config: `architectures` names the class, the backbone's
+    fields lie at the top level).  The backbone fields go through the same checks as the GLiClass importers'; everything the engine does not
+    build is refused with a message that names the field.  Mirrors the sequence-classification block at the end of parse_config in
+    host/glc_safetensors.c."""
+    import dataclasses
+    arch = root.get("architectures") or []
+    if not any(str(a).endswith("ForSequenceClassification") for a in arch):
+        raise ValueError(f"architectures {arch} names no *ForSequenceClassification class")
+    mt = root.get("model_type")
+    if mt not in SEQCLS_MODEL_TYPES:
+        raise ValueError(f"model_type '{mt}' has no sequence-classification head in this engine ({', '.join(SEQCLS_MODEL_TYPES)}; decoder and T5 "
+                         "classes are out of scope)")
+    K = _num_labels(root)
+    if not 1 <= K <= CLS_MAX_LABELS:
+        raise ValueError(f"num_labels {K} is not implemented (1 .. {CLS_MAX_LABELS})")
+    # (a bare HF config: no GLiClass wrapper keys; a key HF wrote as null counts as absent)
+    bare = {k: v for k, v in root.items() if v is not None and k not in ("class_token_index", "text_token_index", "scorer_type", "pooling_strategy", "encoder_config")}
+    if mt in BERT_MODEL_TYPES:
+        base = bert_config_from_hf(bare, vocab=vocab)
+        head = dict(pooling=POOL_FIRST, cls_act=CLS_ACT_TANH, cls_norm=0, cls_dense=1)
+    elif mt == "modernbert":
+        base = modernbert_config_from_hf(bare, vocab=vocab)
+        act = root.get("classifier_activation", "gelu")
+        if act != "gelu":
+            raise ValueError(f"classifier_activation '{act}' is not implemented (gelu)")
+        cp = root.get("classifier_pooling", "cls")
+        if cp not in ("cls", "mean"):
+            raise ValueError(f"classifier_pooling '{cp}' is not implemented (cls, mean)")
+        head = dict(pooling=POOL_FIRST if cp == "cls" else POOL_AVG, cls_act=CLS_ACT_GELU, cls_norm=1, cls_dense=1)
+    else:
+        base = deberta_config_from_hf(bare, vocab=vocab)
+        phs = int(root.get("pooler_hidden_size", base.hidden))
+        if phs != base.hidden:
+            raise ValueError(f"pooler_hidden_size {phs} != hidden_size {base.hidden} is not implemented")
+        act = root.get("pooler_hidden_act", "gelu")
+        if act != "gelu":
+            raise ValueError(f"pooler_hidden_act '{act}' is not implemented (gelu)")
+        head = dict(pooling=POOL_FIRST, cls_act=CLS_ACT_GELU, cls_norm=0, cls_dense=1)
+    return dataclasses.replace(base, head_kind=HEAD_SEQCLS, cls_labels=K, **head)
+
+
+def deberta_config_from_hf(root: dict, vocab: int = None) -> GLiClassConfig:
+    """GLiClassConfig of a bare DebertaV2Config (deberta-v2 / deberta-v3 checkpoints): the disentangled-attention settings every published
+    deberta-v3 has; everything else is refused with a message that names the field.  Mirrors the "deberta-v2" branch of parse_config in
+    host/glc_safetensors.c, field for field; tests/test_seqcls_host.py::test_c_reader_and_python_importer_agree and
+    ::test_importer_refusals_name_the_field run both on the same checkpoints and the same refused fields."""
+    if root.get("model_type") != "deberta-v2":
+        raise ValueError(f"model_type '{root.get('model_type')}' is not deberta-v2")
+    if not root.get("relative_attention", False):
+        raise ValueError("relative_attention=false is not implemented (true)")
+    pat = root.get("pos_att_type") or []
+    pat = pat.split("|") if isinstance(pat, str) else list(pat)
+    if sorted(pat) != ["c2p", "p2c"]:
+        raise ValueError(f"pos_att_type {pat} is not implemented (p2c|c2p)")
+    if not root.get("share_att_key", False):
+        raise ValueError("share_att_key=false is not implemented (true)")
+    if "layer_norm" not in str(root.get("norm_rel_ebd", "none")):
+        raise ValueError(f"norm_rel_ebd '{root.get('norm_rel_ebd')}' is not implemented (layer_norm)")
+    if root.get("position_biased_input", True):
+        raise ValueError("position_biased_input=true is not implemented (false)")
+    if int(root.get("conv_kernel_size", 0) or 0) > 0:
+        raise ValueError(f"conv_kernel_size {root.get('conv_kernel_size')} is not implemented (0)")
+    if int(root.get("type_vocab_size", 0) or 0) > 0:
+        raise ValueError(f"type_vocab_size {root.get('type_vocab_size')} is not implemented (0)")
+    if int(root.get("embedding_size", root["hidden_size"])) != int(root["hidden_size"]):
+        raise ValueError(f"embedding_size {root.get('embedding_size')} != hidden_size is not implemented")
+    act = root.get("hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"hidden_act '{act}' is not implemented (gelu)")
+    H, nh = int(root["hidden_size"]), int(root["num_attention_heads"])
+    if H % nh or H // nh != 64:
+        raise ValueError(f"head_dim {H // nh} is not implemented (64)")
+    mrp = int(root.get("max_relative_positions", -1))
+    if mrp < 1:
+        mrp = int(root.get("max_position_embeddings", 512))
+    vocab = int(vocab if vocab is not None else root["vocab_size"])
+    return GLiClassConfig(name="checkpoint", vocab=vocab, hidden=H, layers=int(root["num_hidden_layers"]), heads=nh, inter=int(root["intermediate_size"]),
+                          pos_buckets=int(root.get("position_buckets", -1)) if int(root.get("position_buckets", -1)) > 0 else 0, max_rel_pos=mrp,
+                          ln_eps=float(root.get("layer_norm_eps", 1e-7)), pad_id=int(root.get("pad_token_id", 0)),
+                          cls_id=int(root.get("cls_token_id", root.get("bos_token_id", 1)) or 1), sep_id=int(root.get("sep_token_id", root.get("eos_token_id", 2)) or 2),
+                          backbone=BACKBONE_DEBERTA)
+
+
+def modernbert_config_from_hf(root: dict, vocab: int = None) -> GLiClassConfig:
+    """GLiClassConfig of a bare ModernBertConfig; everything the engine does not build is refused with a message that names the field.
+    Mirrors the "modernbert" branch of parse_config in host/glc_safetensors.c (both forms of the configuration), held to it by the same
+    two tests as deberta_config_from_hf."""
+    if root.get("model_type") != "modernbert":
+        raise ValueError(f"model_type '{root.get('model_type')}' is not modernbert")
+    for f in ("attention_bias", "mlp_bias", "norm_bias"):
+        if root.get(f, False):
+            raise ValueError(f"{f}=true is not implemented (false)")
+    act = root.get("hidden_activation", "gelu")
+    if act != "gelu":
+        raise ValueError(f"hidden_activation '{act}' is not implemented (gelu)")
+    H, nh = int(root["hidden_size"]), int(root["num_attention_heads"])
+    if H % nh or H // nh != 64:
+        raise ValueError(f"head_dim {H // nh} is not implemented (64)")
+    la = int(root.get("local_attention", 128))
+    if la < 0 or la % 2:
+        raise ValueError(f"local_attention {la} is not implemented (an even window)")
+    # (both forms of configuration_modernbert.py: global_attn_every_n_layers / global_rope_theta / local_rope_theta, or layer_types / rope_parameters)
+    L = int(root["num_hidden_layers"])
+    every = int(root.get("global_attn_every_n_layers", 3))
+    lt = root.get("layer_types")
+    if isinstance(lt, list):
+        if len(lt) != L or any(t not in ("full_attention", "sliding_attention") for t in lt):
+            raise ValueError("layer_types must name 'full_attention' or 'sliding_attention' for every layer")
+        full = [l for l in range(1, L) if lt[l] == "full_attention"]
+        every = full[0] if full else max(L, 1)
+        if any((lt[l] == "full_attention") != (l % every == 0) for l in range(L)):
+            raise ValueError("layer_types is not periodic (full attention on every n-th layer from layer 0)")
+    theta_g, theta_l = float(root.get("global_rope_theta", 160000.0)), float(root.get("local_rope_theta") or 10000.0)
+    rp = root.get("rope_parameters")
+    if isinstance(rp, dict):
+        for key in ("full_attention", "sliding_attention"):
+            if isinstance(rp.get(key), dict) and rp[key].get("rope_type", "default") != "default":
+                raise ValueError(f"rope_parameters.{key}.rope_type '{rp[key]['rope_type']}' is not implemented (default)")
+        theta_g = float((rp.get("full_attention") or {}).get("rope_theta", theta_g))
+        theta_l = float((rp.get("sliding_attention") or {}).get("rope_theta", theta_l))
+    vocab = int(vocab if vocab is not None else root["vocab_size"])
+    return GLiClassConfig(name="checkpoint", vocab=vocab, hidden=H, layers=int(root["num_hidden_layers"]), heads=nh, inter=int(root["intermediate_size"]),
+                          pos_buckets=0, max_rel_pos=0, ln_eps=float(root.get("norm_eps", 1e-5)), pad_id=int(root.get("pad_token_id", 50283)),
+                          cls_id=int(root.get("cls_token_id", root.get("bos_token_id", 50281))), sep_id=int(root.get("sep_token_id", root.get("eos_token_id", 50282))),
+                          backbone=BACKBONE_MODERNBERT, causal=0, rope_theta=theta_g, local_window=la // 2, global_every=every, rope_theta_local=theta_l)
+
+
+def seqcls_from_state_dict(sd: Dict[str, "np.ndarray"], cfg: GLiClassConfig, model_type: str) -> Dict[str, np.ndarray]:
+    """Backbone tensors under their blob names (from_state_dict: the prefixes `deberta.`, `bert.`, `roberta.`, `model.`) + the head's six slots;
+    a head tensor the class does not have, or has switched off, is left out."""
+    names = [n for n, _, _, _ in tensor_specs(cfg) if not n.startswith("cls.")]
+    out = from_state_dict(sd, cfg, names=names)
+    for blob_name, key in zip(CLS_HEAD_NAMES, _SEQCLS_HEAD_KEYS[model_type]):
+        if key is None or key not in sd:
+            if blob_name in CLS_OPTIONAL_BIASES or key is None:
+                continue
+            raise KeyError(key)
+        v = sd[key]
+        out[blob_name] = v.detach().cpu().float().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32)
+    return out
+
+
+def load_seqcls_checkpoint(path: str) -> Tuple[GLiClassConfig, Dict[str, np.ndarray]]:
+    """An HF directory (config.json + model.safetensors) saved by a DebertaV2 / Bert / Roberta / XLMRoberta / ModernBert
+    ForSequenceClassification model -> (config with head_kind = HEAD_SEQCLS, tensors under blob names).  No GLiClass wrapper keys and no
+    <<LABEL>> / <<SEP>> vocabulary rows are expected."""
+    import json
+    import os
+    from safetensors.numpy import load_file
+    with open(os.path.join(path, "config.json")) as f:
+        root = json.load(f)
+    seqcls_config_from_hf(root, vocab=1)                      # (the refusals, before the file is read)
+    sd = load_file(os.path.join(path, "model.safetensors"))
+    emb = [v for k, v in sd.items() if k.endswith("embeddings.word_embeddings.weight") or k.endswith("embeddings.tok_embeddings.weight")]
+    if not emb:
+        raise KeyError("embeddings.word_embeddings.weight")
+    cfg = seqcls_config_from_hf(root, vocab=emb[0].shape[0])
+    return cfg, seqcls_from_state_dict(sd, cfg, root["model_type"])

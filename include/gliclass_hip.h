@@ -70,7 +70,15 @@ typedef struct glc_model_config {
     /* T5 backbone: relative_attention_num_buckets and relative_attention_max_distance of the bias table (bidirectional buckets).  0 on every
      * other backbone. */
     int32_t rel_buckets, rel_max_distance;
+    /* Head kind: GLC_HEAD_GLICLASS (0, every field below 0) or GLC_HEAD_SEQCLS, the head of an HF *ForSequenceClassification checkpoint on the
+     * DeBERTa, BERT and ModernBERT backbones (refused on the decoder and T5 backbones): pooled row ('first' or 'avg' pooling) -> [dense H x H ->]
+     * activation -> [LayerNorm, epsilon ln_eps ->] classifier, fp32 logits [B, cls_labels].  cls_labels = K in 1 .. 1024; cls_act: GLC_CLS_ACT_*;
+     * cls_norm / cls_dense: 0 / 1.  The class-token and scorer fields are not read by this head. */
+    int32_t head_kind, cls_labels, cls_act, cls_norm, cls_dense;
 } glc_model_config;
+enum { GLC_HEAD_GLICLASS = 0, GLC_HEAD_SEQCLS = 1 };
+enum { GLC_CLS_ACT_NONE = 0, GLC_CLS_ACT_TANH = 1, GLC_CLS_ACT_GELU = 2 /* erf form */ };
+#define GLC_CLS_MAX_LABELS 1024
 
 /* Tensor order expected in `tensors[]` (all fp32, row-major, nn.Linear weights are [out,in]):
  *   0 embeddings.word_embeddings.weight [vocab,H]      1,2 embeddings.LayerNorm.{weight,bias}
@@ -121,7 +129,20 @@ static inline int glc_dec_tensors_per_layer(const glc_model_config* c) { return 
  *   then encoder.final_layer_norm.weight [H], then the same 8 head tensors */
 #define GLC_T5_TENSORS_FIXED 2
 #define GLC_T5_TENSORS_PER_LAYER 6
-static inline int glc_num_tensors_cfg(const glc_model_config* c) {
+/* Sequence-classification head (head_kind = GLC_HEAD_SEQCLS): behind the backbone tensors, IN PLACE of the 8 projector tensors and the scorer's,
+ * always GLC_TENSORS_CLS_HEAD slots (all fp32; the arithmetic with its transformers sources is in csrc/cls_head.hip):
+ *   0 dense.weight [H,H]   1 dense.bias [H]                 both NULL when cls_dense = 0; dense.bias alone may be NULL (ModernBERT classifier_bias = false)
+ *   2 norm.weight [H]      3 norm.bias [H]                  both NULL when cls_norm = 0; norm.bias alone may be NULL (ModernBERT norm_bias = false)
+ *   4 classifier.weight [K,H]   5 classifier.bias [K]       the bias may be NULL
+ * A NULL slot is a tensor the checkpoint does not have; every other tensor of the list must be present.  Blob names: the same with the prefix
+ * "cls." (gliclass/c_amd/weights.py); a version-7 blob records only the tensors that exist.
+ * This is the first head of the repository whose logits are pinned end to end on transformers' own numbers (tests/golden/seqcls). */
+#define GLC_TENSORS_CLS_HEAD 6
+static inline int glc_num_head_tensors(const glc_model_config* c) {
+    return c->head_kind == GLC_HEAD_SEQCLS ? GLC_TENSORS_CLS_HEAD : GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
+}
+/* tensors of a configuration with the GLiClass head (the backbone's, the 8 projector tensors, the scorer's) */
+static inline int glc_num_tensors_gliclass(const glc_model_config* c) {
     if (c->backbone == GLC_BACKBONE_T5)
         return GLC_T5_TENSORS_FIXED + GLC_T5_TENSORS_PER_LAYER * c->layers + 1 + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     if (c->backbone == GLC_BACKBONE_BERT)
@@ -130,6 +151,11 @@ static inline int glc_num_tensors_cfg(const glc_model_config* c) {
         return 3 + GLC_MB_TENSORS_PER_LAYER * c->layers - (c->layers > 0 ? 1 : 0) + GLC_TENSORS_HEAD + glc_num_scorer_tensors(c->scorer);
     return (c->backbone == GLC_BACKBONE_DECODER ? 2 + glc_dec_tensors_per_layer(c) * c->layers + GLC_TENSORS_HEAD : glc_num_tensors(c->layers)) +
            glc_num_scorer_tensors(c->scorer);
+}
+/* ... and of any configuration: the sequence-classification head's slots stand in place of the projector and scorer tensors */
+static inline int glc_num_tensors_cfg(const glc_model_config* c) {
+    return c->head_kind == GLC_HEAD_SEQCLS ? glc_num_tensors_gliclass(c) - GLC_TENSORS_HEAD - glc_num_scorer_tensors(c->scorer) + GLC_TENSORS_CLS_HEAD
+                                           : glc_num_tensors_gliclass(c);
 }
 /* index of layer l's first tensor (attn_norm for l > 0, Wqkv for l = 0) in the ModernBERT order */
 static inline int glc_mb_layer_base(int l) { return l == 0 ? 2 : 2 + GLC_MB_TENSORS_PER_LAYER * l - 1; }
@@ -151,6 +177,9 @@ void glc_engine_destroy(glc_engine* e);
  * Blocking; thread-safe per engine (internally serialised, cf. /root/reference/main.c:143-146). */
 int glc_engine_forward(glc_engine* e, const int64_t* ids, const int64_t* mask, int B, int S,
                        float* logits, int c_alloc, int* c_out);
+/* Sequence-classification engines (head_kind = GLC_HEAD_SEQCLS): the same two forwards write logits [B, K], K = cls_labels.  glc_engine_forward
+ * needs c_alloc >= K, writes logits[b*c_alloc + k], k < K (with c_alloc > K the columns k >= K are unspecified), and sets *c_out = K; glc_engine_forward_device needs C == K.  Both fail with a message
+ * otherwise.  The inputs need no <<LABEL>> tokens: class tokens are still scanned for, and what the scan finds is not used. */
 
 /* Device-resident forward (bench / pipelined callers): d_ids, d_mask int64 [B,S] and d_logits
  * f32 [B,C] are device pointers on this engine's device; C = number of class-token slots to score.
@@ -171,6 +200,15 @@ int glc_engine_forward_device(glc_engine* e, const void* d_ids, const void* d_ma
                               void* d_logits);
 int glc_engine_sync(glc_engine* e);
 int glc_engine_device_forward_valid(glc_engine* e);      /* 1 valid / 0 repeat the forward / -1 error; the stream must be idle (see above) */
+
+/* Zero-shot NLI scores on the device (semantics of transformers/pipelines/zero_shot_classification.py postprocess): d_logits f32 [T*Lb, K] are the
+ * logits of the T*Lb (text, hypothesis) pairs, pair (t, l) in row t*Lb + l — what a forward of this engine wrote for that pair batch —, d_probs
+ * f32 [T, Lb] the result; both device pointers on this engine's device.  multi_label = 1: per pair, softmax over the two logits (contra_id,
+ * entail_id) and the entailment share; multi_label = 0: per text, softmax of the entail_id logits over its Lb labels (contra_id is not read).
+ * Max-subtracted exp2 in fp32.  Enqueues on the engine's stream and returns: glc_engine_sync() (or a glc_memcpy_d2h, which is ordered behind
+ * it on that stream) before the host reads d_probs.  Returns 0; -1 with a message in glc_last_error() for a null engine or pointer, a
+ * GLiClass-head engine, K < 2, T < 1, Lb < 1, or entail_id / contra_id outside 0 .. K-1 (multi_label = 1: also entail_id == contra_id). */
+int glc_engine_nli_scores(glc_engine* e, const float* d_logits, int T, int Lb, int entail_id, int contra_id, int multi_label, float* d_probs);
 
 /* Opt-in MX pipeline of the ModernBERT backbone (the DeBERTa and decoder backbones take theirs by default).  Builds the GX copies of the four
  * projection weights of every layer and selects the pipeline: large fp32-mode forwards (the group-split ones) then run their projections on
